@@ -11,6 +11,11 @@ Workload at N=1: BASELINE.json configs[1] (C2): transformer config, 128 Gaussian
 groups), 256x256, batch 32 per GPU x 4 supervised views = 128 rendered views per step.  Weak scaling: every
 rank renders its own 32 objects.  Prints ONE JSON line on rank 0.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) only sets up, warms up, times the N steps of that hot path and prints the
+contract keys (`metric`, `value`, `ms_per_step`, ...).  Everything else below -- per-kernel times and rooflines, repeats, the CPU
+baseline, the train / end-to-end / per-view regions, the other configs, rows N1 / N4a -- runs with `--full`, which also writes
+the full record and prints the compact line with the digest.  `--dump-outputs DIR` writes what the last timed step computed.
+
 `--gpus N` with N > 1 and no torch.distributed.run environment starts the N ranks itself (one process per GPU, localhost
 rendezvous on a free port) the way the reference's launcher does (pointcept/engines/launch.py:75-88); under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` the ranks come from the environment.
@@ -1011,11 +1016,38 @@ def _scale_verdict(world, e2e):
             else f"fail: {sp:.2f} x over one rank's same region < 0.75 x {world}")
 
 
+DUMP_CAP_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirpath, arrays, seed=0):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (float64 stays float64), at most DUMP_CAP_BYTES in all.  Smallest first,
+    each array may fill an equal share of what is left; one larger than its share keeps a seeded sample of its flattened elements -- the
+    same indices in every run, so that two builds compare element for element (no config reaches the cap today: the largest output,
+    C5_fused's gradient, is 32 MB)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in host.items()}
+    left = DUMP_CAP_BYTES - 4096 * len(host)            # (room for the .npy headers)
+    for i, (k, v) in enumerate(sorted(host.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(host) - i)
+        if v.nbytes > share:
+            v = v.reshape(-1)[np.sort(np.random.default_rng(seed).choice(v.size, share // v.itemsize, replace=False))]
+        left -= v.nbytes
+        np.save(os.path.join(dirpath, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel times and rooflines, repeats, CPU baseline, the secondary regions, other configs and "
+                         "rows N1 / N4a, the full record (bench_full.json) and the compact line with their digest; the options below that "
+                         "select among those act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, dL/d(head output)) as DIR/<name>.npy")
     ap.add_argument("--config", default="C2", choices=sorted(synthetic.CONFIGS))
     ap.add_argument("--compact", action="store_true", help="secondary compact-splat regime (SURVEY 8d)")
     ap.add_argument("--two-pass", action="store_true", help="separate forward and backward launch sequences (images kept)")
@@ -1032,6 +1064,8 @@ def main():
     ap.add_argument("--next-rows-only", action="store_true", help="ONLY the N1 / N4a regions (profiling runs: rocprofv3 of this prints their kernels alone)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     a = ap.parse_args()
+    if a.value_region == "train" and not a.full:
+        ap.error("--value-region train quotes the train region, which runs with --full")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no torch.distributed.run environment: start the ranks ourselves, one per GPU (pointcept/engines/launch.py:75-88)
@@ -1054,20 +1088,21 @@ def main():
     B, P, V, H, W, level = cfg["B"], cfg["P"], cfg["V"], cfg["H"], cfg["W"], cfg["level"]
     host_batch = synthetic.make_batch(B, P, V, H, W, level=level, seed=42 + rank, compact=a.compact)
     batch = host_batch.to(dev)
-    feat_dim = 384 if level == "object" else 64
-    torch.manual_seed(42)  # identical initial weights on every rank
-    model = dp.GaussianHead(feat_dim, 128 if level == "object" else 32).to(dev)
-    # The trainable head of the secondary regions (train_step_with_head): synthetic backbone features, final layer standardised per
-    # channel so that its output starts at the N(0,1) statistics of SURVEY 8d (mean 0, std 1 in every one of the 23 channels).
-    feats = torch.randn(B, P, feat_dim, generator=torch.Generator().manual_seed(1000 + rank)).to(dev)
-    with torch.no_grad():
-        raw0 = model(feats)                                     # (B, 23, P)
-        # rounds 0-1 timed the hot path on THIS tensor scaled to unit overall std with the bias dropped -- whose channels are not
-        # N(0,1): opacity channel mean +1.0 / std 0.8, i.e. more opaque, shallower tiles than SURVEY 8d's draw.  Kept as an extra.
-        head_out_r1 = ((raw0 - model.final[2].bias[None, :, None]) / raw0.std()).permute(0, 2, 1).contiguous()
-        mu, sd = raw0.mean(dim=(0, 2)), raw0.std(dim=(0, 2))
-        model.final[2].weight.div_(sd[:, None])
-        model.final[2].bias.copy_((model.final[2].bias - mu) / sd)
+    if a.full:
+        feat_dim = 384 if level == "object" else 64
+        torch.manual_seed(42)  # identical initial weights on every rank
+        model = dp.GaussianHead(feat_dim, 128 if level == "object" else 32).to(dev)
+        # The trainable head of the secondary regions (train_step_with_head): synthetic backbone features, final layer standardised per
+        # channel so that its output starts at the N(0,1) statistics of SURVEY 8d (mean 0, std 1 in every one of the 23 channels).
+        feats = torch.randn(B, P, feat_dim, generator=torch.Generator().manual_seed(1000 + rank)).to(dev)
+        with torch.no_grad():
+            raw0 = model(feats)                                     # (B, 23, P)
+            # rounds 0-1 timed the hot path on THIS tensor scaled to unit overall std with the bias dropped -- whose channels are not
+            # N(0,1): opacity channel mean +1.0 / std 0.8, i.e. more opaque, shallower tiles than SURVEY 8d's draw.  Kept as an extra.
+            head_out_r1 = ((raw0 - model.final[2].bias[None, :, None]) / raw0.std()).permute(0, 2, 1).contiguous()
+            mu, sd = raw0.mean(dim=(0, 2)), raw0.std(dim=(0, 2))
+            model.final[2].weight.div_(sd[:, None])
+            model.final[2].bias.copy_((model.final[2].bias - mu) / sd)
     loss_kind = "focal_l2" if level == "object" else "l2"
 
     from unipre3d_amd.fused import backward_unit, render_loss_fused
@@ -1118,7 +1153,33 @@ def main():
         for _ in range(20):
             hot_step()
         torch.cuda.synchronize()
+    # (the event scopes stay in a plain run too: `value` is quoted on this region exactly as before --full existed)
     elapsed, prof, loss = timed(hot_step, True, prof_stride=4)   # every 4th launch of the dominant kernel carries events
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"loss": loss, "grad_head_out": head_out.grad})
+    NV = B * V
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "rendered_views_per_sec", "value": world * NV * a.steps / elapsed, "unit": "views/s", "n_gpus": world,
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{a.config}: render-loss hot path (activations + render fwd + loss + render bwd), {level}-level, P={P} Gaussians/object, {H}x{W}, "
+                                   f"B={B}/GPU x V={V} views = {NV} renders/GPU/step; head output o ~ N(0,1) i.i.d. (SURVEY 8d primary regime)"
+                                   + (", scaling channels -4 + 0.5 N(0,1) (compact-splat regime)" if a.compact else ""),
+                       "global_batch": B * world, "views_per_step": NV * world, "parallelism": f"dp{world}",
+                       "loss": loss_kind, "path": "unfused (torch activations/loss)" if a.unfused else "fused head-activation + render + loss (HIP)",
+                       "autograd_entry": "loss.backward()"},
+            "final_loss": float(loss),
+        }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(out, separators=(",", ":")), flush=True)
+        if world > 1:
+            dp.host_barrier()
+            dp.shutdown()
+        return
+
     # run-to-run spread of the same K-step region (not `value`: five further repeats without the event scopes)
     reps = sorted(1e3 * timed(hot_step, False, warmup=0)[0] / a.steps for _ in range(5))
     # host cost of issuing one step (the launches of 16 steps against an empty queue, before any synchronisation)
@@ -1188,7 +1249,6 @@ def main():
         color, radii, _ = rasterize_gaussians_batched(g["xyz"], g["opacity"], batch.world_view, batch.full_proj, batch.camera_center,
                                                       batch.bg, H, W, t, t, shs=head.concat_sh(g["features_dc"], g["features_rest"]),
                                                       scales=g["scaling"], rotations=g["rotation"], sh_degree=1)
-    out = None
     if rank == 0:
         tiles = ((W + 15) // 16) * ((H + 15) // 16)
         # R from the Gaussian rects: visible Gaussians x tiles touched is accumulated by the kernel; read it back via radii>0
@@ -1197,7 +1257,6 @@ def main():
         with torch.no_grad():   # R of the Gaussians the timed steps actually rendered
             g_used = synthetic.gaussians_from_batch(synthetic.SyntheticBatch(**dict(batch.__dict__, raw=head_out.detach().permute(0, 2, 1))))
         R_mean, walk_stats = _read_num_rendered(g_used, batch, H, W, t)
-        NV = B * V
         kernels = {}
         for k, (ms, cnt) in prof.items():
             if cnt:
@@ -1212,23 +1271,13 @@ def main():
         fb_ms = sum(kernels[k]["avg_ms"] for k in kernels)
         fwd_bytes = (168.0 * P + 76.0 * R_mean + 8.0 * tiles + 24.0 * H * W) * NV
         bwd_bytes = (308.0 * P + 76.0 * R_mean + 24.0 * H * W) * NV
-        out = {
-            "metric": "rendered_views_per_sec", "value": world * NV * a.steps / elapsed, "unit": "views/s", "n_gpus": world,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{a.config}: render-loss hot path (activations + render fwd + loss + render bwd), {level}-level, P={P} Gaussians/object, {H}x{W}, "
-                                   f"B={B}/GPU x V={V} views = {NV} renders/GPU/step; head output o ~ N(0,1) i.i.d. (SURVEY 8d primary regime)"
-                                   + (", scaling channels -4 + 0.5 N(0,1) (compact-splat regime)" if a.compact else ""),
-                       "global_batch": B * world, "views_per_step": NV * world, "parallelism": f"dp{world}",
-                       "loss": loss_kind, "num_rendered_per_view": R_mean, "list_consumption": walk_stats,
-                       "path": "unfused (torch activations/loss)" if a.unfused else "fused head-activation + render + loss (HIP)",
-                       "autograd_entry": "loss.backward()"},
+        out["config"].update(num_rendered_per_view=R_mean, list_consumption=walk_stats)
+        out.update({
             "render_loss_step_ms": {"rasterizer_kernels_total": fb_ms, "kernels": kernels},
-            "final_loss": float(loss),
             "repeatability": {"what": f"five further repeats of the same {a.steps}-step timed region, ms per step", "min": reps[0], "median": reps[2],
                               "max": reps[4], "timed_region_ms": 1e3 * elapsed},
             "hot_step_host_issue_us": host_us,
-        }
+        })
         default_path = not (a.unfused or a.two_pass)
         prof_cfg = a.config + ("_compact" if a.compact else "")
         if dom:

@@ -22,6 +22,7 @@ any distance -- the far-depth scene sits at 58 x) or stays under the tighter abs
 """
 from __future__ import annotations
 
+import contextlib
 import math
 
 import numpy as np
@@ -191,6 +192,20 @@ def assert_radii(rd, r32, r64=None, what=""):
         return 0, 0
     r64 = np.asarray(r64)
     return int((rd != r64).sum()), int((r32 != r64).sum())
+
+
+@contextlib.contextmanager
+def one_tile_per_thread(oracle_mod, H, W):
+    """The oracle's backward deals its 16 x 16 tiles to the OpenMP team round-robin and adds the threads' partial sums in thread order,
+    so its fp32 result -- the yardstick of worst_fp32_sample -- depends on the team size, i.e. on the host (OMP_NUM_THREADS, core
+    count).  With one thread per tile every tile's sum stands alone and the tiles are added in tile order, on any host: the grouping
+    of the many-core hosts the scene-level bars were set on."""
+    n0 = oracle_mod.num_threads()
+    oracle_mod.set_num_threads(((H + 15) // 16) * ((W + 15) // 16))
+    try:
+        yield
+    finally:
+        oracle_mod.set_num_threads(n0)
 
 
 def worst_fp32_sample(samples, o64):

@@ -72,3 +72,22 @@ def test_scale_verdict_sentences():
     assert b._scale_verdict(8, {"value": 1.0, "rccl_ranks": 8, "speedup_over_n1_same_region": 7.41}) == "pass: 7.41 x over one rank's same region >= 0.75 x 8"
     assert b._scale_verdict(8, {"value": 1.0, "rccl_ranks": 8, "speedup_over_n1_same_region": 5.2}).startswith("fail: 5.20 x")
     assert b._scale_verdict(4, {"value": 1.0, "rccl_ranks": 4}).startswith("fail: no single-rank time")
+
+
+def test_dump_outputs_sample_beyond_the_cap(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files; arrays beyond the 64 MB cap together keep the same seeded sample in every run."""
+    import numpy as np
+    import torch
+    b = _bench()
+    small = torch.arange(6, dtype=torch.float64).reshape(2, 3)
+    big = torch.randn(18 * 2 ** 20, generator=torch.Generator().manual_seed(0))             # 72 MB of float32
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"small": small, "big": big, "ints": torch.arange(5, dtype=torch.int32)})
+    sizes = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert sizes <= b.DUMP_CAP_BYTES
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and s.shape == (2, 3) and np.array_equal(s, small.numpy())        # under the cap's share: whole
+    assert np.load(tmp_path / "a" / "ints.npy").dtype == np.float32
+    ba, bb = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert ba.dtype == np.float32 and 0 < ba.size < big.numel() and np.array_equal(ba, bb)
+    assert np.isin(ba[:100], big.numpy()).all()

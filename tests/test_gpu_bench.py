@@ -51,7 +51,7 @@ def _run(args, env=None, timeout=900, compact=False):
 
 
 def test_bench_line_single_gpu_small_config():
-    out = _run(["--config", "C1", "--steps", "5", "--warmup", "2", "--cpu-seconds", "1", "--no-e2e"])
+    out = _run(["--full", "--config", "C1", "--steps", "5", "--warmup", "2", "--cpu-seconds", "1", "--no-e2e"])
     for k in CONTRACT + ("cpu_baseline",):
         assert k in out, k
     assert out["n_gpus"] == 1 and out["steps"] == 5 and out["scaling"] == "weak" and out["dtype"] == "f32"
@@ -67,7 +67,7 @@ def test_bench_line_single_gpu_small_config():
 
 
 def test_bench_self_launches_two_ranks():
-    out, line = _run(["--gpus", "2", "--config", "C1", "--steps", "4", "--warmup", "1", "--cpu-seconds", "1"],
+    out, line = _run(["--full", "--gpus", "2", "--config", "C1", "--steps", "4", "--warmup", "1", "--cpu-seconds", "1"],
                      env={"U3D_BENCH_SHARE_GPU": "1", "U3D_BENCH_EXTRAS_BUDGET_S": "240"}, compact=True)
     assert out["n_gpus"] == 2 and out["config"]["parallelism"] == "dp2" and out["config"]["views_per_step"] == 16
     # an N > 1 line is field for field as complete as the N = 1 line: roofline AND cpu_baseline (rank 0 times it
@@ -96,7 +96,7 @@ def test_bench_self_launches_two_ranks():
     assert out["train_region_value"] == e2e["value"] and out["n1_same_region"] == e2e["n1_same_region"]["value"]
     assert out["gradient_bytes_all_reduced_per_step"] == 4 * 29_464_215 and out["speedup_over_n1_same_region"] > 0
     # the same launch quoting the step WITH the exchange in it as `value`
-    out2 = _run(["--gpus", "2", "--config", "C1", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--value-region", "train"],
+    out2 = _run(["--full", "--gpus", "2", "--config", "C1", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--value-region", "train"],
                 env={"U3D_BENCH_SHARE_GPU": "1", "U3D_BENCH_EXTRAS_BUDGET_S": "240"})
     e = out2["train_step_e2e_standin"]
     assert out2["value"] == e["value"] and out2["ms_per_step"] == e["ms_per_step"] and out2["hot_path"]["value"] > out2["value"]
@@ -110,7 +110,7 @@ def test_bench_under_torch_distributed_run():
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1",
            "--no-cpu-baseline", "--no-e2e", "--no-next-rows"]
     import tempfile
     with tempfile.TemporaryDirectory() as td:
@@ -132,7 +132,7 @@ def test_bench_under_torch_distributed_run():
 def test_default_line_carries_the_other_configs_and_the_noop_control():
     """The driver's own command (`python bench.py --gpus 1`, here with fewer steps): after the contractual C2 region the line
     holds the hot-only steps of C3 / C4 / C5 / C2-compact (`other_configs`) and the per-view route's NO-OP-operator control."""
-    out, line = _run(["--steps", "10", "--warmup", "3", "--cpu-seconds", "1", "--no-e2e"], compact=True)
+    out, line = _run(["--full", "--steps", "10", "--warmup", "3", "--cpu-seconds", "1", "--no-e2e"], compact=True)
     ex = line["extra_keys"]
     assert "extra_keys_dropped" not in line, line.get("extra_keys_dropped")
     assert set(ex["other_configs"]) == {"C3", "C4", "C5", "C2_compact", "C4_fused", "C5_fused"} and len(ex["pointops_us"]) >= 14
@@ -166,3 +166,30 @@ def test_default_line_carries_the_other_configs_and_the_noop_control():
     assert po["ops"]["fps_1024_to_128"]["us_per_selection"] < 0.6                          # (0.84 before round 5; 0.44 measured)
     for half in ("forward", "backward"):
         assert fu[half]["us"] > 0 and fu[half]["equals_oracle"] and fu[half]["cpu_baseline"]["value"] > 0
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints only the contract's headline keys, times exactly --steps steps, writes no full record, and
+    --dump-outputs holds the last timed step's loss and dL/d(head output): seeded inputs, so two runs dump the same arrays."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600,
+                             env=dict(os.environ, U3D_BENCH_FULL_JSON=str(tmp_path / "bench_full.json")))
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and lines[0] == res.stdout.rstrip("\n").splitlines()[-1]
+        line = json.loads(lines[0])
+        assert line["metric"] == "rendered_views_per_sec" and line["unit"] == "views/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f32" and line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+        assert abs(line["value"] - 8 * 3 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]
+        assert "roofline" not in line and "cpu_baseline" not in line and "extra_keys" not in line
+        assert not (tmp_path / "bench_full.json").exists()
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("loss", "grad_head_out")})
+    g = dumps[0]["grad_head_out"]
+    assert g.dtype == np.float32 and g.shape == (2, 128, 23) and np.isfinite(g).all() and np.abs(g).sum() > 0
+    assert abs(float(dumps[0]["loss"]) - line["final_loss"]) <= 1e-6 * abs(line["final_loss"])
+    assert float(dumps[0]["loss"]) == float(dumps[1]["loss"])
+    assert np.abs(dumps[0]["grad_head_out"] - dumps[1]["grad_head_out"]).max() <= 1e-6 * np.abs(g).max()

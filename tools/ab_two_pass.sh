@@ -3,7 +3,7 @@
 LIBS=${1:-"lib"}; CFGS=${2:-"C2"}
 cd $GRAFT_REPO_ROOT
 for c in $CFGS; do for l in $LIBS; do
-  U3D_BENCH_FULL_JSON=/tmp/ab2_full.json U3D_LIB_DIRNAME=$l python bench.py --config $c --two-pass --hot-only --no-cpu-baseline --steps 50 --warmup 10 >/dev/null 2>&1
+  U3D_BENCH_FULL_JSON=/tmp/ab2_full.json U3D_LIB_DIRNAME=$l python bench.py --full --config $c --two-pass --hot-only --no-cpu-baseline --steps 50 --warmup 10 >/dev/null 2>&1
   python -c "
 import json
 d=json.load(open('/tmp/ab2_full.json'))

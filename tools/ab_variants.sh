@@ -4,7 +4,7 @@
 # (reads the FULL record of the run -- bench_full.json -- the stdout line is the compact contract object since round 6)
 LIBS=${1:-"lib"}; CFGS=${2:-"C2"}; shift 2
 for c in $CFGS; do for l in $LIBS; do
-  U3D_BENCH_FULL_JSON=/tmp/ab_full.json U3D_LIB_DIRNAME=$l python bench.py --config $c --hot-only --no-cpu-baseline --steps 50 --warmup 10 "$@" >/dev/null 2>&1
+  U3D_BENCH_FULL_JSON=/tmp/ab_full.json U3D_LIB_DIRNAME=$l python bench.py --full --config $c --hot-only --no-cpu-baseline --steps 50 --warmup 10 "$@" >/dev/null 2>&1
   python -c "
 import json
 d=json.load(open('/tmp/ab_full.json'))

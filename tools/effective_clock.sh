@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r06t; mkdir -p $O; export TMPDIR=/tmp
 for c in ${1:-C2}; do
   rm -rf /tmp/clk_$c
-  rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_INSTS_VALU --kernel-trace --output-format csv -d /tmp/clk_$c -- python bench.py --config $c --steps 6 --warmup 2 --no-cpu-baseline --hot-only > /tmp/clk_$c.log 2>&1
+  rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_INSTS_VALU --kernel-trace --output-format csv -d /tmp/clk_$c -- python bench.py --full --config $c --steps 6 --warmup 2 --no-cpu-baseline --hot-only > /tmp/clk_$c.log 2>&1
   python - $c <<'PY' | tee $O/effective_clock_$c.json
 import csv, glob, json, sys
 c = sys.argv[1]

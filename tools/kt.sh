@@ -1,9 +1,10 @@
 #!/bin/bash
 # per-kernel average durations (rocprofv3 kernel trace) of the bench: tools/kt.sh <tag> [bench args]
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 tag=$1; shift
 rm -rf /tmp/kt_$tag
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$tag -- python $GRAFT_REPO_ROOT/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-e2e "$@" > /tmp/kt_$tag.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$tag -- python $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-e2e "$@" > /tmp/kt_$tag.log 2>&1
 f=$(find /tmp/kt_$tag -name "*kernel_stats.csv" | head -1)
 python - "$f" "$tag" <<'PY'
 import csv, sys, re

@@ -6,7 +6,7 @@
 #               4 heaviest first within each view, views interleaved (what a production form could compute per view in preprocess_fwd)
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r06g; mkdir -p $O
 for rep in 1 2; do for m in 0 1 2 3 4; do for c in C2; do
-  U3D_LPT_MODE=$m U3D_LIB_DIRNAME=lib_lpt U3D_BENCH_FULL_JSON=/tmp/g.json python bench.py --config $c --hot-only --no-cpu-baseline --steps 50 --warmup 10 > /dev/null 2> /tmp/g.err
+  U3D_LPT_MODE=$m U3D_LIB_DIRNAME=lib_lpt U3D_BENCH_FULL_JSON=/tmp/g.json python bench.py --full --config $c --hot-only --no-cpu-baseline --steps 50 --warmup 10 > /dev/null 2> /tmp/g.err
   grep "\[lpt\]" /tmp/g.err | tail -1
   python -c "
 import json

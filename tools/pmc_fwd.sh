@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; cd /tmp; export TMPDIR=/tmp
 i=0
 for P in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU"; do
   i=$((i+1)); rm -rf /tmp/pf_$i
-  rocprofv3 --pmc $P --kernel-trace --output-format csv -d /tmp/pf_$i -- python $R/bench.py --config ${1:-C2} --steps 6 --warmup 2 --no-cpu-baseline --hot-only > /tmp/pf_$i.log 2>&1
+  rocprofv3 --pmc $P --kernel-trace --output-format csv -d /tmp/pf_$i -- python $R/bench.py --full --config ${1:-C2} --steps 6 --warmup 2 --no-cpu-baseline --hot-only > /tmp/pf_$i.log 2>&1
 done
 python - <<'PY'
 import csv, glob, collections

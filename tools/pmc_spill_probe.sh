@@ -8,10 +8,10 @@ CFG=${1:-C2}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r03; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 probe() {   # $1 = tag
   for c in WRITE_SIZE FETCH_SIZE; do
-    rm -rf /tmp/sp_$1_$c; rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/sp_$1_$c -- python $R/bench.py --config $CFG --steps 10 --warmup 3 --no-cpu-baseline --hot-only > /tmp/sp_$1_$c.log 2>&1
+    rm -rf /tmp/sp_$1_$c; rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/sp_$1_$c -- python $R/bench.py --full --config $CFG --steps 10 --warmup 3 --no-cpu-baseline --hot-only > /tmp/sp_$1_$c.log 2>&1
     cp $(find /tmp/sp_$1_$c -name "*counter_collection.csv" | head -1) /tmp/sp_$1_$c.csv
   done
-  rm -rf /tmp/sp_$1_kt; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/sp_$1_kt -- python $R/bench.py --config $CFG --steps 30 --warmup 5 --no-cpu-baseline --hot-only > /tmp/sp_$1_kt.log 2>&1
+  rm -rf /tmp/sp_$1_kt; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/sp_$1_kt -- python $R/bench.py --full --config $CFG --steps 30 --warmup 5 --no-cpu-baseline --hot-only > /tmp/sp_$1_kt.log 2>&1
   cp $(find /tmp/sp_$1_kt -name "*kernel_stats.csv" | head -1) /tmp/sp_$1_kt.csv
 }
 probe pinned

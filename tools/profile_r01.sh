@@ -2,11 +2,11 @@
 # Regenerates the judged artifacts of the default bench (C2 single-pass): kernel stats, bench line, PMC traffic.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py --steps 50 --warmup 10 > $O/bench_line.json 2> $O/bench.err
-rm -rf /tmp/kt; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline --hot-only > $O/kt.log 2>&1
+python $R/bench.py --full --steps 50 --warmup 10 > $O/bench_line.json 2> $O/bench.err
+rm -rf /tmp/kt; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $R/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --hot-only > $O/kt.log 2>&1
 cp $(find /tmp/kt -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf /tmp/pmc_$c; rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --hot-only > $O/pmc_$c.log 2>&1
+  rm -rf /tmp/pmc_$c; rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -- python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --hot-only > $O/pmc_$c.log 2>&1
   cp $(find /tmp/pmc_$c -name "*counter_collection.csv" | head -1) /tmp/cc_$c.csv
 done
 python - <<'PY' > $O/pmc_traffic.json

@@ -11,13 +11,13 @@ EXTRA=$3; CFG=$CFGNAME; if [ -n "$EXTRA" ]; then CFG=${CFGNAME}_${EXTRA#--}; fi
 if [ -n "$U3D_LIB_DIRNAME" ] && [ "$U3D_LIB_DIRNAME" != "lib" ]; then CFG=${CFG}_${U3D_LIB_DIRNAME}; fi
 cd /tmp && export TMPDIR=/tmp
 ARGS="--config $CFGNAME $EXTRA --steps 50 --warmup 10"
-if [ "$CFG" = "C2" ]; then U3D_BENCH_FULL_JSON=$O/bench_full_$CFG.json python $R/bench.py $ARGS > $O/bench_line_$CFG.json 2> $O/bench_$CFG.err
-else U3D_BENCH_FULL_JSON=$O/bench_full_$CFG.json python $R/bench.py $ARGS --hot-only --cpu-seconds 10 > $O/bench_line_$CFG.json 2> $O/bench_$CFG.err; fi
+if [ "$CFG" = "C2" ]; then U3D_BENCH_FULL_JSON=$O/bench_full_$CFG.json python $R/bench.py --full $ARGS > $O/bench_line_$CFG.json 2> $O/bench_$CFG.err
+else U3D_BENCH_FULL_JSON=$O/bench_full_$CFG.json python $R/bench.py --full $ARGS --hot-only --cpu-seconds 10 > $O/bench_line_$CFG.json 2> $O/bench_$CFG.err; fi
 if [ -n "$ONLY_LINE" ]; then tail -c 300 $O/bench_line_$CFG.json; echo; exit 0; fi   # (second pass: lines regenerated once this round's PMC / SQ files are committed)
-rm -rf /tmp/kt_$CFG; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$CFG -- python $R/bench.py $ARGS --no-cpu-baseline --hot-only > $O/kt_$CFG.log 2>&1
+rm -rf /tmp/kt_$CFG; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$CFG -- python $R/bench.py --full $ARGS --no-cpu-baseline --hot-only > $O/kt_$CFG.log 2>&1
 cp $(find /tmp/kt_$CFG -name "*kernel_stats.csv" | head -1) $O/kernel_stats_bench_$CFG.csv
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf /tmp/pmc_$c; rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -- python $R/bench.py --config $CFGNAME $EXTRA --steps 10 --warmup 3 --no-cpu-baseline --hot-only > $O/pmc_${c}_$CFG.log 2>&1
+  rm -rf /tmp/pmc_$c; rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -- python $R/bench.py --full --config $CFGNAME $EXTRA --steps 10 --warmup 3 --no-cpu-baseline --hot-only > $O/pmc_${c}_$CFG.log 2>&1
   cp $(find /tmp/pmc_$c -name "*counter_collection.csv" | head -1) /tmp/cc_$c.csv
 done
 python - $CFG <<'PY' > $O/pmc_traffic_$CFG.json
@@ -43,7 +43,7 @@ print(json.dumps({
 PY
 if [ "$CFG" = "C2" ]; then
   for c in FETCH_SIZE WRITE_SIZE; do
-    rm -rf /tmp/pmcf_$c; rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmcf_$c -- python $R/bench.py --config C2 --steps 5 --warmup 2 --no-cpu-baseline --hot-only > $O/pmcf_${c}.log 2>&1
+    rm -rf /tmp/pmcf_$c; rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmcf_$c -- python $R/bench.py --full --config C2 --steps 5 --warmup 2 --no-cpu-baseline --hot-only > $O/pmcf_${c}.log 2>&1
     cp $(find /tmp/pmcf_$c -name "*counter_collection.csv" | head -1) /tmp/ccf_$c.csv
   done
   python - <<'PY' > $O/pmc_traffic_fwd_C2.json
@@ -69,7 +69,7 @@ if [ "$2" = "sq" ]; then
   i=0
   for P in "$P1" "$P2"; do
     i=$((i+1)); rm -rf /tmp/sq_$i
-    rocprofv3 --pmc $P --kernel-trace --output-format csv -d /tmp/sq_$i -- python $R/bench.py --config $CFGNAME $EXTRA --steps 6 --warmup 2 --no-cpu-baseline --hot-only > $O/sq_${i}_$CFG.log 2>&1
+    rocprofv3 --pmc $P --kernel-trace --output-format csv -d /tmp/sq_$i -- python $R/bench.py --full --config $CFGNAME $EXTRA --steps 6 --warmup 2 --no-cpu-baseline --hot-only > $O/sq_${i}_$CFG.log 2>&1
     cp $(find /tmp/sq_$i -name "*counter_collection.csv" | head -1) /tmp/sq_$i.csv
   done
   python - $CFG $O <<'PY' > $O/sq_issue_$CFG.json
@@ -93,7 +93,7 @@ PY
   i=2
   for P in "$P3" "$P4"; do
     i=$((i+1)); rm -rf /tmp/sq_$i
-    rocprofv3 --pmc $P --kernel-trace --output-format csv -d /tmp/sq_$i -- python $R/bench.py --config $CFGNAME $EXTRA --steps 6 --warmup 2 --no-cpu-baseline --hot-only > $O/sq_${i}_$CFG.log 2>&1
+    rocprofv3 --pmc $P --kernel-trace --output-format csv -d /tmp/sq_$i -- python $R/bench.py --full --config $CFGNAME $EXTRA --steps 6 --warmup 2 --no-cpu-baseline --hot-only > $O/sq_${i}_$CFG.log 2>&1
     cp $(find /tmp/sq_$i -name "*counter_collection.csv" | head -1) /tmp/sq_$i.csv
   done
   python - $CFG <<'PY' > $O/sq_wait_$CFG.json

@@ -1,8 +1,9 @@
 #!/bin/bash
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 tag=$1; shift
 rm -rf /tmp/tl_$tag
-rocprofv3 --kernel-trace --output-format csv -d /tmp/tl_$tag -- python $GRAFT_REPO_ROOT/bench.py --steps 30 --warmup 5 --no-cpu-baseline --hot-only "$@" > /tmp/tl_$tag.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/tl_$tag -- python $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --hot-only "$@" > /tmp/tl_$tag.log 2>&1
 f=$(find /tmp/tl_$tag -name "*kernel_trace.csv" | head -1)
 python - "$f" "$tag" <<'PY'
 import csv, sys, re
