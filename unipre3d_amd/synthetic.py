@@ -4,6 +4,7 @@ activations (head.py, R1), cameras from the reference's matrix formulas (cameras
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Dict
 
@@ -100,3 +101,62 @@ def single_view_scene(P: int = 64, H: int = 48, W: int = 64, seed: int = 0, leve
                 viewmatrix=b.world_view[0, 0].contiguous(), projmatrix=b.full_proj[0, 0].contiguous(),
                 campos=b.camera_center[0, 0].contiguous(), bg=b.bg.clone(), image_height=H, image_width=W,
                 tanfovx=t, tanfovy=t, sh_degree=sh_degree)
+
+
+def point_fusion_scene(V: int = 8, H: int = 120, W: int = 160, C: int = 32, seed: int = 0, n_init: int = 4096,
+                       hole_rate: float = 0.05, focal_scale: float = 1.0):
+    """Seeded scene-level fusion inputs (fusion/point_fusion.py:36-43) with realistic voxel sharing: each view's depth map is the
+    nearest hit of its pixel rays on a 6 x 5 x 3 m room (floor, ceiling, four walls) and a few axis-aligned boxes, unprojected
+    with computeUnprojection's formula (dataset/scannet.py:639-671: x = (u - cx) z / fx, y = (v - cy) z / fy, valid = z > 5 cm;
+    ScanNet's intrinsics scaled to W, times `focal_scale`: a narrower view makes small images share voxels as full-size ones do).
+    A `hole_rate` share of the pixels has no depth (invalid).  init_coord samples the valid
+    points below 2.6 m, so ceiling pixels fall outside its box.
+    Returns dict feat_2d_all (V,C,H,W), unprojected_coord (1,V,H,W,4), init_coord (n_init,3), c2w (V,4,4), all fp32 on the CPU."""
+    g = torch.Generator().manual_seed(seed)
+    room = torch.tensor([6.0, 5.0, 3.0])
+    lo_b = torch.rand(4, 3, generator=g) * torch.tensor([4.5, 3.5, 0.0]) + torch.tensor([0.5, 0.5, 0.0])
+    hi_b = lo_b + torch.rand(4, 3, generator=g) * torch.tensor([1.0, 1.0, 1.2]) + torch.tensor([0.3, 0.3, 0.3])
+    fx = fy = 577.87 * W / 640.0 * focal_scale
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    u = torch.arange(W, dtype=torch.float32).view(1, -1).expand(H, W)
+    v = torch.arange(H, dtype=torch.float32).view(-1, 1).expand(H, W)
+    dirs_cam = torch.stack([(u - cx) / fx, (v - cy) / fy, torch.ones(H, W)], -1).reshape(-1, 3)   # unit depth per ray
+    out, c2ws = [], []
+    for _ in range(V):
+        eye = torch.rand(3, generator=g) * torch.tensor([3.0, 2.5, 0.6]) + torch.tensor([1.5, 1.25, 1.2])
+        yaw = float(torch.rand(1, generator=g)) * 2 * math.pi
+        pitch = -0.2 - 0.3 * float(torch.rand(1, generator=g))
+        fwd = torch.tensor([math.cos(yaw) * math.cos(pitch), math.sin(yaw) * math.cos(pitch), math.sin(pitch)])
+        right = torch.linalg.cross(fwd, torch.tensor([0.0, 0.0, 1.0]))
+        right = right / right.norm()
+        down = torch.linalg.cross(fwd, right)
+        R = torch.stack([right, down, fwd], 1)                       # camera x right, y down, z forward
+        c2w = torch.eye(4)
+        c2w[:3, :3], c2w[:3, 3] = R, eye
+        d = dirs_cam @ R.T                                           # world direction per unit camera depth
+        # depth of the nearest surface: the room's planes from inside, then the boxes (slab test)
+        with torch.no_grad():
+            inv = 1.0 / torch.where(d.abs() < 1e-9, torch.full_like(d, 1e-9), d)
+            t_room = torch.where(d > 0, (room - eye) * inv, (0 - eye) * inv).min(1).values
+            t = t_room
+            for b in range(lo_b.shape[0]):
+                t0, t1 = (lo_b[b] - eye) * inv, (hi_b[b] - eye) * inv
+                tn, tf = torch.minimum(t0, t1).max(1).values, torch.maximum(t0, t1).min(1).values
+                hit = (tn <= tf) & (tn > 0)
+                t = torch.where(hit & (tn < t), tn, t)
+        depth = t.reshape(H, W)
+        depth = torch.where(torch.rand(H, W, generator=g) < hole_rate, torch.zeros_like(depth), depth)
+        z = depth
+        x = (u - cx) * z / fx
+        y = (v - cy) * z / fy
+        cam = torch.stack([x, y, z, torch.ones_like(z)], -1).reshape(-1, 4).T
+        world = (c2w @ cam)[:3]
+        valid = (cam[2] > 5e-2).float()
+        out.append(torch.cat([world, valid.unsqueeze(0)], 0).T.reshape(H, W, 4))
+        c2ws.append(c2w)
+    uc = torch.stack(out).unsqueeze(0).contiguous()
+    pts = uc.reshape(-1, 4)
+    pts = pts[(pts[:, 3] != 0) & (pts[:, 2] < 2.6)][:, :3]
+    init = pts[torch.randint(0, pts.shape[0], (n_init,), generator=g)].contiguous()
+    feat = torch.randn(V, C, H, W, generator=g)
+    return {"feat_2d_all": feat, "unprojected_coord": uc, "init_coord": init, "c2w": torch.stack(c2ws)}
