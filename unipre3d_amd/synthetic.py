@@ -160,3 +160,49 @@ def point_fusion_scene(V: int = 8, H: int = 120, W: int = 160, C: int = 32, seed
     init = pts[torch.randint(0, pts.shape[0], (n_init,), generator=g)].contiguous()
     feat = torch.randn(V, C, H, W, generator=g)
     return {"feat_2d_all": feat, "unprojected_coord": uc, "init_coord": init, "c2w": torch.stack(c2ws)}
+
+
+def sparse_voxel_scene(batch: int = 2, voxel: float = 0.036, seed: int = 0, channels: int = 6):
+    """Seeded surface-like sparse voxel input for the scene backbones (occupancy of real scans, not uniform noise): per batch item
+    the floor, ceiling and four walls of a 6 x 5 x 3 m room, a few axis-aligned boxes and two spheres, sampled at half the voxel
+    size and voxelized.  Rows are in ascending (batch, d0, d1, d2) order.  Returns dict indices (N,4) int32 (batch, d0, d1, d2),
+    spatial_shape [D0, D1, D2], batch_size, features (N, channels) N(0,1), all on the CPU (about 115 k voxels per item at 3.6 cm)."""
+    g = torch.Generator().manual_seed(seed)
+    room = torch.tensor([6.0, 5.0, 3.0])
+    h = voxel / 2
+
+    def plane(a, b, axis, at, lo=(0.0, 0.0)):   # points of the plane axis = at over [lo, lo + (a, b)] in the other two axes
+        u = torch.arange(0.0, a, h) + lo[0]
+        v = torch.arange(0.0, b, h) + lo[1]
+        uu, vv = torch.meshgrid(u, v, indexing="ij")
+        cols = [uu.reshape(-1), vv.reshape(-1)]
+        cols.insert(axis, torch.full_like(cols[0], at))
+        return torch.stack(cols, 1)
+
+    items = []
+    for bi in range(batch):
+        pts = [plane(6.0, 5.0, 2, 0.0), plane(6.0, 5.0, 2, 2.98), plane(5.0, 3.0, 0, 0.0), plane(5.0, 3.0, 0, 5.98),
+               plane(6.0, 3.0, 1, 0.0), plane(6.0, 3.0, 1, 4.98)]
+        for _ in range(3):
+            lo = torch.rand(3, generator=g) * torch.tensor([4.0, 3.0, 0.0]) + 0.5
+            sz = torch.rand(3, generator=g) * torch.tensor([1.0, 1.0, 1.0]) + 0.4
+            for ax in range(3):
+                o = [a for a in range(3) if a != ax]
+                for at in (lo[ax], lo[ax] + sz[ax]):
+                    p = plane(float(sz[o[0]]), float(sz[o[1]]), ax, float(at), (float(lo[o[0]]), float(lo[o[1]])))
+                    pts.append(p)
+        for _ in range(2):
+            c = torch.rand(3, generator=g) * torch.tensor([4.0, 3.0, 1.0]) + torch.tensor([1.0, 1.0, 1.0])
+            r = 0.3 + 0.4 * float(torch.rand(1, generator=g))
+            n = int(4 * math.pi * r * r / (h * h))
+            d = torch.randn(n, 3, generator=g)
+            pts.append(c + r * d / d.norm(dim=1, keepdim=True))
+        p = torch.cat(pts)
+        p = p + (torch.rand(p.shape, generator=g) - 0.5) * (0.2 * voxel)
+        p = torch.minimum(torch.maximum(p, torch.zeros(3)), room - 1e-4)
+        q = torch.floor(p / voxel).long()
+        items.append(torch.cat([torch.full((q.shape[0], 1), bi, dtype=torch.long), q], 1))
+    shape = [int(math.ceil(float(x) / voxel)) for x in room]
+    idx = torch.unique(torch.cat(items), dim=0)   # sorted rows: ascending (batch, d0, d1, d2)
+    return {"indices": idx.to(torch.int32).contiguous(), "spatial_shape": shape, "batch_size": batch,
+            "features": torch.randn(idx.shape[0], channels, generator=g)}
