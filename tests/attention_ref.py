@@ -47,6 +47,153 @@ CASES = {
 }
 
 
+# ---- structured cases: the structure is a property of the inputs (make_structured); test_attention_ref.py asserts it on fp64 scores -----
+# name -> (sequence lengths, tail rows, heads, max_seqlen, softmax_scale).  Every case starts from make_inputs(lengths, tail, H, 1.0,
+# STRUCT_SEED) and applies the transformation in make_structured.  U16 is the fixed direction (+-1/4 per component, |U16| = 1).
+STRUCT_SEED = 2
+NEG_LENS = (1, 15, 17, 47, 49, 65, 130, 1009)
+PEAK_LENS = (17, 48, 64, 65, 129, 1009, 1024)
+HOT_LENS = (32, 16, 5, 9, 31, 1, 12, 17, 0, 2)
+STRUCTURED = {
+    "all_negative": (NEG_LENS, 3, 3, 1009, SCALE),
+    "all_positive": (NEG_LENS, 3, 3, 1009, SCALE),
+    "peak_last_key": (PEAK_LENS, 0, 2, 1024, SCALE),
+    "rising_max": ((300, 1024), 2, 2, 1024, SCALE),
+    "uniform_q0": ((48, 17, 1, 64, 65, 300), 1, 5, 300, SCALE),
+    "uniform_k_equal": ((48, 17, 1, 64, 65, 300), 1, 5, 300, SCALE),
+    "one_hot": (HOT_LENS, 0, 5, 32, SCALE),
+    "one_hot_p200": (HOT_LENS, 0, 5, 200, SCALE),          # the same rows through the workgroup-per-head path
+    "scale_neg": (MIXED, 7, 2, 1024, -0.25),
+    "scale_zero": (MIXED, 7, 2, 1024, 0.0),
+    "scale_2": (MIXED, 7, 2, 1024, 2.0),
+    "v_large": ((48, 17, 1, 64, 130, 513), 2, 3, 513, SCALE),
+    "subnormal": ((48, 17, 1, 64, 130), 2, 2, 130, SCALE),
+    "dout_zero": (MIXED, 7, 2, 1024, SCALE),
+}
+# Magnitudes (the largest power of two, found on the CPU, at which attention_rounded against attention_fp64 keeps the forward inside
+# ONE of the three forward units and the backward yardstick finite and not above the largest one of CASES, 51.76 ulp; a case that
+# needs more says why).  The reached property values are those printed by test_attention_ref.py::test_structured_case.
+NEG_A = 16.0        # all_negative / all_positive: q = eps/2 + A u, k = eps/2 -+ A u: every real q.k <= -NEG, reached NEG = 205.1 (>= 32 =
+                    # 8 / |scale|; all_positive: every q.k >= 206.6).  A = 32 and 64 also keep the forward inside one unit (0.60, 0.56)
+                    # but need 108.7 and 236.4 ulp: sum_j dS_ij = 0 cancels the common component A u of the keys in dq (and of the
+                    # queries in dk), so every dq / dk block has a true gradient far below |dS| |k|.  A = 16 is the largest that
+                    # stays under the largest yardstick of CASES.
+PEAK_C = 8.0        # peak_last_key: q += C u, then the last key = B * mean of the sequence's q: reached margin over the second key 23.68
+PEAK_B = 4.0        # (scaled score units).  From B = 4 on every row is one-hot to fp16 precision (the restatement's forward error is 0),
+                    # so a larger B changes nothing; B = 2 (margin 9.69) needs 57.0 ulp, above the largest yardstick of CASES.
+RISE_C = 8.0        # rising_max: q += C u, keys sorted by k.u ascending, key j += R * (j // 64) * u: the 64-key step maximum of every row
+RISE_R = 12.0       # rises by at least 15.26 log2 units per step (required: 4).  R = 24 (rise 30.1) needs 63.5 ulp: not taken.
+HOT_C = 8.0         # one_hot: k_j = eps/4 +- B e_(j mod 16) (sign - from key 16 on), q_i += +-C e at its hot key (L - 1 - i): reached margin
+HOT_B = 64.0        # 44.97 (scaled score units): softmax rows are one-hot, the true dq / dk vanish and block_den's floor carries the bar
+V_LARGE_MUL = 2.0 ** 13     # v_large: v *= 2^13: reached max|v| = 32864, inside [3e4, 6e4] (2^14 would overflow fp16)
+V_LARGE_DOUT = 2.0 ** -1    # dO *= 2^-1: reached max|dS| = 12266, a factor 5 below the fp16 maximum (24531 with dO as given, which leaves a
+                            # kernel that places its roundings differently less than a factor 3)
+SUBNORMAL_MUL = 2.0 ** -15  # subnormal: qkv *= 2^-15: 95.6 % of the values are fp16 subnormals.  2^-16 (and so 2^-20) cannot keep an fp16 output
+SUBNORMAL_DOUT = 2.0 ** 13  # inside one forward unit: out is subnormal, its rounding alone is 2^-25 against a unit of 2^-11 max|v| = 2^-25.
+                            # dO *= 2^13 (the largest power of two that keeps dO finite) so that dq, dk ~ |dS| |k| are not flushed.
+# attention_rounded's normalised backward error on make_structured(case), in units of 2^-11, measured on the CPU and recorded 10 % up like
+# BWD_YARDSTICK_ULPS (re-derived by test_attention_ref.py).  uniform_k_equal: sum_j dS_ij k = 0, the true dq is exactly 0 and its
+# blocks stand on block_den's floor.  dout_zero: every gradient is exactly 0.
+STRUCTURED_YARDSTICK_ULPS = {"all_negative": 6.64, "all_positive": 6.67, "peak_last_key": 0.97, "rising_max": 27.56,
+                             "uniform_q0": 1.24, "uniform_k_equal": 33.59, "one_hot": 0.12, "one_hot_p200": 0.12, "scale_neg": 1.83,
+                             "scale_zero": 1.16, "scale_2": 4.5, "v_large": 1.42, "subnormal": 26.1, "dout_zero": 0.0}
+
+
+def _u16():
+    return torch.tensor([1, -1, 1, 1, -1, 1, -1, -1, 1, 1, -1, 1, -1, -1, 1, -1], dtype=torch.float32) / 4.0
+
+
+def _hot_index(i, L):
+    """the key that query i of a length-L sequence points at"""
+    return (L - 1 - i) % L
+
+
+def make_structured(name, seed=STRUCT_SEED):
+    """(qkv, dout, cu_seqlens, max_seqlen, softmax_scale) of a STRUCTURED case: fp16 CPU tensors, reproducible.  Rows beyond
+    cu_seqlens[-1] (the tail) keep their Gaussian values."""
+    lens, tail, H, max_seqlen, scale = STRUCTURED[name]
+    qkv, dout, cu = make_inputs(lens, tail, H, 1.0, seed)
+    x, g, u = qkv.float(), dout.float(), _u16()
+    for a, b in zip(cu[:-1].tolist(), cu[1:].tolist()):
+        L = b - a
+        if L == 0:
+            continue
+        q, k, v = x[a:b, 0], x[a:b, 1], x[a:b, 2]                     # views (L, H, 16)
+        if name in ("all_negative", "all_positive"):
+            q.mul_(0.5).add_(NEG_A * u)
+            k.mul_(0.5).add_((-NEG_A if name == "all_negative" else NEG_A) * u)
+        elif name == "peak_last_key":
+            q.add_(PEAK_C * u)
+            k[L - 1] = PEAK_B * q.half().float().mean(0)
+        elif name == "rising_max":
+            q.add_(RISE_C * u)
+            order = torch.argsort(k @ u, dim=0)                         # (L, H): ascending score with the probe u
+            k.copy_(torch.gather(k, 0, order[..., None].expand(-1, -1, 16)))
+            k.add_((RISE_R * (torch.arange(L) // 64).float())[:, None, None] * u)
+        elif name == "uniform_q0":
+            q.zero_()
+        elif name == "uniform_k_equal":
+            k.copy_(k[:1].expand(L, -1, -1).clone())
+        elif name in ("one_hot", "one_hot_p200"):
+            j = torch.arange(L)
+            sign = torch.where(j < 16, 1.0, -1.0)
+            k.mul_(0.25)
+            k[j, :, j % 16] += (HOT_B * sign)[:, None]
+            hot = torch.tensor([_hot_index(i, L) for i in range(L)])
+            q[j, :, hot % 16] += (HOT_C * sign[hot])[:, None]
+    if name == "v_large":
+        x[:, 2] *= V_LARGE_MUL
+        g *= V_LARGE_DOUT
+    elif name == "subnormal":
+        x *= SUBNORMAL_MUL
+        g *= SUBNORMAL_DOUT
+    elif name == "dout_zero":
+        g.zero_()
+    return x.half(), g.half(), cu, max_seqlen, scale
+
+
+def structured_property(name, qkv, cu, scale):
+    """the value that states the case's structure, from the fp64 scores q.k of the fp16-valued inputs (None: the case has none);
+    the requirement on it is asserted by test_attention_ref.py"""
+    x = qkv.double()
+    worst = None
+    for a, b in zip(cu[:-1].tolist(), cu[1:].tolist()):
+        L = b - a
+        if L == 0:
+            continue
+        s = torch.einsum("qhd,khd->hqk", x[a:b, 0], x[a:b, 1])        # raw scores (H, L, L)
+        if name == "all_negative":                                      # NEG: minus the largest real score
+            val = float(-s.max())
+        elif name == "all_positive":
+            val = float(s.min())
+        elif name == "peak_last_key":                                   # margin of the last key over the best other key, scaled units
+            if L == 1:
+                continue
+            val = float((s[..., -1] - s[..., :-1].amax(-1)).min() * scale)
+        elif name == "rising_max":                                      # smallest rise of the 64-key step maximum, log2 units
+            steps = torch.stack([s[..., c:c + 64].amax(-1) for c in range(0, L, 64)], -1) * (scale * 1.4426950408889634)
+            val = float((steps[..., 1:] - steps[..., :-1]).min())
+        elif name in ("one_hot", "one_hot_p200"):                       # margin of the hot key over the best other key, scaled units
+            if L == 1:
+                continue
+            hot = torch.tensor([_hot_index(i, L) for i in range(L)])
+            top = torch.gather(s, 2, hot[None, :, None].expand(s.shape[0], -1, 1))[..., 0]
+            rest = s.scatter(2, hot[None, :, None].expand(s.shape[0], -1, 1), float("-inf")).amax(-1)
+            val = float((top - rest).min() * scale)
+        elif name in ("uniform_q0", "uniform_k_equal"):                 # spread of a row's scores: exactly 0
+            val = float((s.amax(-1) - s.amin(-1)).max())
+            val = -val
+        else:
+            break
+        worst = val if worst is None else min(worst, val)
+    if name == "v_large":
+        return float(qkv[:int(cu[-1]), 2].double().abs().max())
+    if name == "subnormal":                                             # fraction of fp16 subnormals among the nonzero values
+        r = qkv[:int(cu[-1])].double().abs()
+        return float(((r < 2.0 ** -14) & (r > 0)).double().mean())
+    return worst
+
+
 def cu_from_lengths(lengths):
     return np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))]).astype(np.int32)
 

@@ -135,3 +135,17 @@ def subm_table_np(indices, spatial_shape, k):
                 T[hit, t] = order[p[hit]]
                 t += 1
     return T
+
+
+def chains_np(indices, spatial_shape):
+    """(first, next) int64 over the rows of each site: first[r] the lowest row at r's site, next[r] the next higher row there or -1."""
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1, 4)
+    keys = _lin(idx, [int(d) for d in spatial_shape])
+    order = np.argsort(keys, kind="stable")
+    sk = keys[order]
+    first, nxt = np.empty(len(idx), np.int64), np.full(len(idx), -1, np.int64)
+    head = np.concatenate([[True], sk[1:] != sk[:-1]]) if len(idx) else np.zeros(0, bool)
+    first[order] = order[np.maximum.accumulate(np.where(head, np.arange(len(idx)), 0))] if len(idx) else 0
+    same = ~head[1:] if len(idx) else head
+    nxt[order[:-1][same]] = order[1:][same]
+    return first, nxt

@@ -79,3 +79,61 @@ def test_backward_yardstick_constants(name):
     assert measured <= recorded <= 1.3 * measured
     assert bool(((o.double() - o64).abs() <= R.fwd_bound(qkv, cu) / R.FWD_UNITS).all())
     assert R.bwd_bar(recorded * R.ULP16) == 2 * recorded * R.ULP16 + R.ULP16
+
+
+# what each structured case must reach, on the fp64 scores of its fp16-valued inputs (attention_ref.structured_property)
+STRUCTURED_REQUIRED = {
+    "all_negative": lambda p, scale: p >= 8.0 / abs(scale),     # every real score <= -NEG: exp(-NEG |scale|) is below an fp16 ulp
+    "all_positive": lambda p, scale: p >= 8.0 / abs(scale),
+    "peak_last_key": lambda p, scale: p > 0,                     # the arg-max key of every row is len - 1
+    "rising_max": lambda p, scale: p >= 4.0,                     # log2 units per 64-key step
+    "uniform_q0": lambda p, scale: p == 0,                       # every row's scores are exactly equal
+    "uniform_k_equal": lambda p, scale: p == 0,
+    "one_hot": lambda p, scale: p >= 8.0,                        # every other key's weight is below an fp16 ulp
+    "one_hot_p200": lambda p, scale: p >= 8.0,
+    "v_large": lambda p, scale: 3e4 <= p <= 6e4,
+    "subnormal": lambda p, scale: p > 0.5,                       # most values are fp16 subnormals
+}
+
+
+def test_structured_table():
+    assert set(R.STRUCTURED) == set(R.STRUCTURED_YARDSTICK_ULPS)
+    heads = {c[2] for c in R.STRUCTURED.values()}
+    assert len(heads) >= 2 and any(h % 4 for h in heads)
+    for name in ("scale_neg", "scale_zero", "scale_2", "dout_zero"):      # the mixed_h2 inputs
+        assert R.STRUCTURED[name][:4] == R.CASES["mixed_h2"][:4]
+    assert [R.STRUCTURED[n][4] for n in ("scale_neg", "scale_zero", "scale_2")] == [-0.25, 0.0, 2.0]
+    assert R.STRUCTURED["all_negative"][0] == (1, 15, 17, 47, 49, 65, 130, 1009)
+    assert R.STRUCTURED["peak_last_key"][0] == (17, 48, 64, 65, 129, 1009, 1024) and R.STRUCTURED["rising_max"][0] == (300, 1024)
+    for name, (lens, tail, H, max_seqlen, scale) in R.STRUCTURED.items():
+        qkv, dout, cu, ms, sc = R.make_structured(name)
+        assert qkv.dtype == torch.float16 and dout.dtype == torch.float16 and qkv.shape == (sum(lens) + tail, 3, H, 16)
+        assert ms == max_seqlen >= max(lens) and sc == scale and bool(torch.isfinite(qkv).all()) and bool(torch.isfinite(dout).all())
+        assert torch.equal(qkv, R.make_structured(name)[0])
+    assert not R.make_structured("dout_zero")[1].any()
+    assert not R.make_structured("uniform_q0")[0][:-1, 0].any()
+
+
+@pytest.mark.parametrize("name", list(R.STRUCTURED))
+def test_structured_case(name):
+    """The structure of the case holds on the fp64 scores; STRUCTURED_YARDSTICK_ULPS is re-derived exactly like BWD_YARDSTICK_ULPS and
+    the forward restatement stays inside one of the three units of the forward bar."""
+    qkv, dout, cu, _, scale = R.make_structured(name)
+    prop = R.structured_property(name, qkv, cu, scale)
+    o64, d64 = R.attention_fp64(qkv, cu, scale, dout)
+    o, d = R.attention_rounded(qkv, cu, scale, dout)
+    assert bool(torch.isfinite(o).all()) and bool(torch.isfinite(d).all()) and bool(torch.isfinite(d64).all())
+    assert float(d64.abs().max()) < 65504 / 2, "the true gradient must sit well inside the fp16 range"
+    measured = R.bwd_norm_err(d, d64, R.block_den(qkv, dout, d64, cu, scale)) / R.ULP16
+    recorded = R.STRUCTURED_YARDSTICK_ULPS[name]
+    unit = R.fwd_bound(qkv, cu) / R.FWD_UNITS
+    units = float(((o.double() - o64).abs() / unit.clamp_min(1e-300)).max())
+    print(f"[attention_ref] {name}: property {prop}, forward {units:.3f} unit, yardstick measured {measured:.3f} ulp, recorded {recorded}")
+    if name in STRUCTURED_REQUIRED:
+        assert prop is not None and STRUCTURED_REQUIRED[name](prop, scale), (name, prop)
+    assert measured <= recorded <= 1.3 * measured
+    assert bool(((o.double() - o64).abs() <= unit).all())
+    if name == "dout_zero":
+        assert not d64.any() and not d.any()
+    if name == "scale_zero":
+        assert not d64[:, :2].any() and not d[:, :2].any()

@@ -91,3 +91,44 @@ def test_refusals():
         f(x, ip, reduce="prod")
     with pytest.raises(RuntimeError, match="device"):
         f(x.cpu(), ip.cpu())
+
+
+def test_ptv3_scale_with_one_long_segment():
+    """N = 240 000 rows, C = 64: pooling segments of 1..16 rows and one segment of 50 000 rows, where the bound
+    2^-23 * sum|terms| * segment length is not trivial; all four reductions, forward and backward."""
+    g = np.random.default_rng(240)
+    N, C, LONG = 240_000, 64, 50_000
+    lens = []
+    while sum(lens) < 100_000:
+        lens.append(int(g.integers(1, 17)))
+    lens.append(LONG)
+    while sum(lens) < N - 16:
+        lens.append(int(g.integers(1, 17)))
+    lens.append(N - sum(lens))
+    indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    assert indptr[-1] == N and max(lens) == LONG and sorted(lens)[-2] <= 16 and min(lens) >= 1
+    M = len(lens)
+    src = g.normal(size=(N, C)).astype(np.float32)
+    src[g.integers(0, N, 4000), g.integers(0, C, 4000)] = 1.5   # ties
+    dout = g.normal(size=(M, C)).astype(np.float32)
+    seglen = np.diff(indptr).astype(np.float64)[:, None]
+    sabs, _ = R.segment_csr_ref(np.abs(src), indptr, "sum")
+    for reduce in REDUCES:
+        x = torch.as_tensor(src).to(DEV).requires_grad_(True)
+        out = _sc().segment_csr(x, torch.as_tensor(indptr).to(DEV), reduce=reduce)
+        assert out.shape == (M, C) and out.dtype == torch.float32
+        out.backward(torch.as_tensor(dout).to(DEV))
+        ref, arg = R.segment_csr_ref(src, indptr, reduce)
+        dref = R.segment_csr_grad_ref(dout, indptr, arg, N, reduce)
+        got, dgot = out.detach().cpu().numpy(), x.grad.cpu().numpy()
+        if reduce in ("max", "min"):
+            assert np.array_equal(got, ref), reduce
+            assert np.array_equal(dgot, dref), f"{reduce}: gradient rows (ties go to the lowest row)"
+        else:
+            bound = 2.0 ** -23 * sabs.astype(np.float64) * seglen
+            if reduce == "mean":
+                bound = bound / np.maximum(seglen, 1) + 2.0 ** -23 * np.abs(ref)
+            err = np.abs(got.astype(np.float64) - ref)
+            print(f"[segment_csr] {reduce}: long segment worst error / bound {float((err[lens.index(LONG)] / bound[lens.index(LONG)]).max()):.3e}")
+            assert np.all(err <= bound), reduce
+            assert np.allclose(dgot, dref, rtol=2.0 ** -22, atol=0), f"{reduce}: gradient"

@@ -146,3 +146,16 @@ def test_sparse_tensor_on_cpu():
 def test_vectorized_table_equals_dictionary_table(k):
     idx, D, _ = _scene(20 + k, n=150, dup=20)
     assert np.array_equal(R.subm_table_np(idx, D, k), R.subm_table(idx, D, k))
+
+
+def test_chains_np_against_dictionaries():
+    g = np.random.default_rng(5)
+    idx = np.concatenate([g.integers(0, 2, size=(400, 1)), g.integers(0, 4, size=(400, 3))], 1)   # 128 cells: long chains
+    first, nxt = R.chains_np(idx, (4, 4, 4))
+    rows = {}
+    for i, s in enumerate(map(tuple, idx)):
+        rows.setdefault(s, []).append(i)
+    for s, rs in rows.items():
+        assert all(first[r] == rs[0] for r in rs)
+        assert [int(nxt[r]) for r in rs] == rs[1:] + [-1]
+    assert R.chains_np(np.zeros((0, 4), np.int64), (4, 4, 4))[0].shape == (0,)

@@ -174,6 +174,8 @@ def down_map(indices, spatial_shape, batch_size, s) -> DownMap:
 def _gemm(R, K, A, W, bias, table, list_row=None, mask=None, out_rows=None):
     """Y (out_rows, Cout): table mode Y[o] = bias + sum_k A[table[o,k]] W[k]; list mode over list_row / table = list_src.  W (K,Cin,Cout)."""
     Cin, Cout = W.shape[1], W.shape[2]
+    if A.shape[0] == 0:   # a strided conv that dropped every row: no entry has a source, the rows are bias (or 0); never read
+        A = A.new_zeros(1, Cin)
     Y = torch.empty(R if out_rows is None else out_rows, Cout, dtype=torch.float32, device=A.device)
     _check(load().u3d_spconv_gemm(R, K, Cin, Cout, _lib.ptr(table), _lib.ptr(list_row), _lib.ptr(A), _lib.ptr(W), _lib.ptr(bias),
                                   _lib.ptr(mask), _lib.ptr(Y), _stream(A.device)), "u3d_spconv_gemm")
