@@ -115,7 +115,8 @@ def test_three_interpolate_forward_backward():
 
 def test_gradient_kernels_beyond_the_lds_rows():
     """The scatter-add gradients accumulate channel rows in LDS (round 5); rows that do not fit 64 KB (n resp. m > 16384) take the
-    global-atomic form, and a shape whose channel count is not a multiple of the rows per workgroup exercises the tail."""
+    global-atomic form.  Every shape here has b * c <= 80 rows, so the LDS kernels run with ONE row per workgroup (CB = 1): this test reaches
+    CB = 1 and the global kernel, and no channel tail.  The classes CB = 2 .. 16 and their tails are in test_gpu_pointops_grad.py."""
     from unipre3d_amd import pointops
     rng = np.random.RandomState(5)
     for (C, N, M, K) in ((3, 20000, 40, 8), (37, 700, 33, 5), (20, 16384, 16, 4)):

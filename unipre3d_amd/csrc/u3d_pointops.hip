@@ -423,11 +423,12 @@ __global__ __launch_bounds__(256) void group_points_grad_lds_kernel(int c, int n
       const float m1 = lane - 1 >= lo ? 1.f : 0.f, m2 = lane - 2 >= lo ? 1.f : 0.f, m4 = lane - 4 >= lo ? 1.f : 0.f, m8 = lane - 8 >= lo ? 1.f : 0.f;
       const float mb15 = ((lane & 16) && rs < (lane & ~15)) ? 1.f : 0.f;  // rows 1 and 3: the run began in an earlier row
       const float mb31 = (lane >= 32 && rs < 32) ? 1.f : 0.f;             // rows 2 and 3: ... before lane 32
-      // 0 x inf = NaN would leak a non-finite value into a NEIGHBOURING run: such waves take the select form
+      // 0 x inf = NaN would leak a non-finite value into a NEIGHBOURING run: such waves take the select form.  Finite inputs are not enough:
+      // 3e38 + 3e38 is +inf after the first step.  Below 2^120 a run's partial sum (<= 64 x chk per channel) cannot reach infinity.
       float chk = 0.f;
 #pragma unroll
       for (int cc = 0; cc < CB; ++cc) chk += fabsf(g[cc]);
-      if (__ballot(!(chk < __builtin_inff())) == 0ull) {
+      if (__ballot(!(chk < 0x1p120f)) == 0ull) {
 #pragma unroll
         for (int cc = 0; cc < CB; ++cc)
           asm volatile("s_nop 1\n\t"
@@ -714,6 +715,22 @@ inline int lds_rows(int len, int b, int c) {
   while (cb * 2 <= 16 && cb * 2 <= fit && cb * 2 <= want) cb *= 2;
   return cb;
 }
+// rows per workgroup the two gradient entry points launch with: lds_rows unless the experiment switch (U3D_GG_CB / U3D_IG_CB, read once per
+// process) names another count that fits 64 KB; 0 -- also for a switch value without an instantiation -- is the global-atomic kernel.
+// Host arithmetic only: the u3d_*_grad_rows queries answer through it without touching the device.
+inline int grad_rows(int len, int b, int c, int env) {
+  int cb = lds_rows(len, b, c);
+  if (env > 0 && cb > 0 && (size_t)env * len * sizeof(float) <= 65536) cb = env;
+  return (cb == 16 || cb == 8 || cb == 4 || cb == 2 || cb == 1) ? cb : 0;
+}
+inline int group_grad_rows(int b, int c, int n) {
+  static const int cb_env = getenv("U3D_GG_CB") ? atoi(getenv("U3D_GG_CB")) : 0;   // (experiment switch)
+  return grad_rows(n, b, c, cb_env);
+}
+inline int interp_grad_rows(int b, int c, int m) {
+  static const int ig_env = getenv("U3D_IG_CB") ? atoi(getenv("U3D_IG_CB")) : 0;   // (experiment switch)
+  return m > 0 ? grad_rows(m, b, c, ig_env) : 0;
+}
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // launch KERNEL<..., CM> for the process-wide contraction mode
@@ -831,9 +848,7 @@ int u3d_group_points_grad(int b, int c, int n, int npoints, int nsample, const f
   if (b > 65535 || c > 65535) return 1;
   if (!grad_out || !idx || !grad_points) return 1;
   const int total = npoints * nsample;
-  int cb = lds_rows(n, b, c);
-  static const int cb_env = getenv("U3D_GG_CB") ? atoi(getenv("U3D_GG_CB")) : 0;   // (experiment switch)
-  if (cb_env > 0 && cb > 0 && (size_t)cb_env * n * sizeof(float) <= 65536) cb = cb_env;
+  const int cb = group_grad_rows(b, c, n);
 #define GG(CB) hipLaunchKernelGGL((group_points_grad_lds_kernel<CB>), dim3((c + CB - 1) / CB, b), dim3(256), sizeof(float) * (size_t)CB * n, \
                                   (hipStream_t)stream, c, n, total, grad_out, idx, grad_points)
   if (cb == 16) GG(16);
@@ -889,9 +904,7 @@ int u3d_three_interpolate_grad(int b, int c, int n, int m, const float* grad_out
   if (b == 0 || c == 0 || n == 0) return 0;
   if (b > 65535 || (c + IC_CH - 1) / IC_CH > 65535) return 1;
   if (!grad_out || !idx || !weight || !grad_points) return 1;
-  int cb = m > 0 ? lds_rows(m, b, c) : 0;
-  static const int ig_env = getenv("U3D_IG_CB") ? atoi(getenv("U3D_IG_CB")) : 0;   // (experiment switch)
-  if (ig_env > 0 && cb > 0 && (size_t)ig_env * m * sizeof(float) <= 65536) cb = ig_env;
+  const int cb = interp_grad_rows(b, c, m);
 #define IG(CB) hipLaunchKernelGGL((three_interpolate_grad_lds_kernel<CB>), dim3((c + CB - 1) / CB, b), dim3(256), sizeof(float) * (size_t)CB * m, \
                                   (hipStream_t)stream, c, n, m, grad_out, idx, weight, grad_points)
   if (cb == 16) IG(16);
@@ -905,6 +918,9 @@ int u3d_three_interpolate_grad(int b, int c, int n, int m, const float* grad_out
                        c, n, m, grad_out, idx, weight, grad_points);
   return hipGetLastError() == hipSuccess ? 0 : 3;
 }
+
+int u3d_group_points_grad_rows(int b, int c, int n) { return group_grad_rows(b, c, n); }
+int u3d_three_interpolate_grad_rows(int b, int c, int m) { return interp_grad_rows(b, c, m); }
 
 int u3d_pointops_set_contraction(int mode) {
   if (mode != U3D_PO_FMA_LLVM && mode != U3D_PO_FMA_CHAIN && mode != U3D_PO_NO_FMA) return 1;

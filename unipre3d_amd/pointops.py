@@ -17,7 +17,7 @@ from . import _lib
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_pointops.so")   # (U3D_LIB_DIRNAME: experiment builds, see _lib.py)
 EXPORTS = ("u3d_furthest_point_sampling", "u3d_ball_query", "u3d_group_points", "u3d_group_points_grad",
            "u3d_gather_points", "u3d_gather_points_grad", "u3d_three_nn", "u3d_three_interpolate", "u3d_three_interpolate_grad",
-           "u3d_pointops_set_contraction", "u3d_pointops_get_contraction")
+           "u3d_pointops_set_contraction", "u3d_pointops_get_contraction", "u3d_group_points_grad_rows", "u3d_three_interpolate_grad_rows")
 CONTRACTIONS = {"fma_llvm": 0, "fma_chain": 1, "none": 2}    # include/unipre3d_pointops.h: U3D_PO_*
 
 
@@ -49,6 +49,8 @@ def load() -> ctypes.CDLL:
         lib.u3d_three_interpolate_grad.argtypes = [i, i, i, i, vp, vp, vp, vp, vp]
         lib.u3d_pointops_set_contraction.argtypes = [i]
         lib.u3d_pointops_get_contraction.argtypes = []
+        lib.u3d_group_points_grad_rows.argtypes = [i, i, i]
+        lib.u3d_three_interpolate_grad_rows.argtypes = [i, i, i]
         for n in EXPORTS:
             getattr(lib, n).restype = ctypes.c_int
         _po = lib
