@@ -1,5 +1,5 @@
-"""C-ABI library: loads without a GPU, exports every symbol include/unipre3d_rasterizer.h declares, host-only
-entry points (scratch query, argument checks) behave.  No compute calls here."""
+"""C-ABI libraries: they load without a GPU, export every symbol their headers declare and are bound as the headers say; the
+rasterizer's host-only entry points (scratch query, argument checks) behave.  No compute calls here."""
 import ctypes
 import os
 import re
@@ -17,19 +17,91 @@ def lib():
     return _lib.load()
 
 
-def _declared_functions():
-    hdr = open(os.path.join(ROOT, "include", "unipre3d_rasterizer.h")).read()
+# header of every native library -> the modules that bind it (attention.py and scatter.py share one library)
+LIBRARIES = {"rasterizer": ("_lib",), "pointops": ("pointops",), "fusion": ("fusion",), "gradclip": ("gradcheck",),
+             "pointfusion": ("pointfusion",), "sparseconv": ("sparseconv",), "attention": ("attention", "scatter"),
+             "serialization": ("serialization",)}
+_DECLARATION = re.compile(r"(?:^|[;}])\s*((?:const\s+)?\w+(?:\s+\w+)?\s*\*?)\s*\b(u3d_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", re.M)
+
+
+def _declared_functions(header="rasterizer"):
+    """{name: (return type, [parameter type, ...])} of every u3d_* function include/unipre3d_<header>.h declares (comments stripped;
+    a pointer parameter's type ends in '*', `(void)` is no parameter)."""
+    hdr = open(os.path.join(ROOT, "include", f"unipre3d_{header}.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(u3d_[a-z_0-9]+)\s*\(", hdr)))
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    hdr = re.sub(r"^\s*#[^\n]*", "", hdr, flags=re.M)
+    out = {}
+    for ret, name, params in _DECLARATION.findall(hdr):
+        types = []
+        for p in (q.strip() for q in params.split(",")):
+            if p in ("", "void"):
+                continue
+            if "*" in p:
+                types.append(p[:p.rindex("*") + 1].replace(" ", ""))
+            else:
+                types.append(" ".join(p.split()[:-1]))        # drop the parameter's name
+        assert name not in out, name
+        out[name] = (" ".join(ret.split()).replace(" *", "*"), types)
+    return out
 
 
 def test_every_declared_symbol_is_exported(lib):
-    names = _declared_functions()
+    names = sorted(_declared_functions())
     assert set(names) == set(_lib.EXPORTS)
     for n in names:
         assert getattr(lib, n) is not None
     assert lib.u3d_abi_version() == _lib.ABI_VERSION == 5
     assert lib.u3d_error_string(0) == b"ok" and b"invalid" in lib.u3d_error_string(1)
+
+
+def _is_pointer(ctype):
+    return ctype is ctypes.c_void_p or issubclass(ctype, ctypes._Pointer)
+
+
+@pytest.mark.parametrize("header", sorted(LIBRARIES))
+def test_header_and_binding_agree(lib, header):
+    """Every library's header against its module's table AND against what the loader set on the opened handle: the names, the
+    parameter count, the return type and the class of every parameter."""
+    import importlib
+    declared = _declared_functions(header)
+    mods = [importlib.import_module("unipre3d_amd." + m) for m in LIBRARIES[header]]
+    assert len(declared) >= 3
+    assert set(declared) == set().union(*(m.EXPORTS for m in mods))
+    for m in mods:
+        assert len(set(m.EXPORTS)) == len(m.EXPORTS)
+    handle = mods[0].load()
+    scalars = {"float": ctypes.c_float, "uint64_t": ctypes.c_uint64, "int": ctypes.c_int, "int32_t": ctypes.c_int32,
+               "long long": ctypes.c_longlong}
+    for name, (ret, params) in declared.items():
+        fn = getattr(handle, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), name
+        want = {"size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}.get(ret, ctypes.c_int)
+        assert ret in ("int", "size_t", "const char*") and fn.restype is want, (name, ret, fn.restype)
+        for k, (c_type, bound) in enumerate(zip(params, fn.argtypes)):
+            if c_type.endswith("*"):
+                assert _is_pointer(bound), (name, k, c_type, bound)
+            else:
+                assert bound is scalars[c_type], (name, k, c_type, bound)
+
+
+def test_loader_failure_modes(lib, tmp_path, monkeypatch):
+    """open_library on a directory of its own: a missing file, a library of another ABI, and the cache."""
+    import shutil
+    from unipre3d_amd import fusion
+    fusion.load()
+    monkeypatch.setattr(_lib, "LIB_DIR", str(tmp_path))
+    missing = os.path.join(str(tmp_path), "libunipre3d_fusion.so")
+    with pytest.raises(RuntimeError, match="no fallback") as e:
+        fusion.load()
+    assert missing in str(e.value)
+    shutil.copy2(fusion.LIB_PATH, missing)
+    with pytest.raises(RuntimeError, match=r"ABI 2, this module binds ABI 3: rebuild"):
+        _lib.open_library("libunipre3d_fusion.so", fusion.SIGNATURES, ("u3d_fusion_abi_version", fusion.ABI_VERSION + 1))
+    first = fusion.load()                                       # the refused handle was not kept
+    assert first is fusion.load() and first.u3d_fusion_abi_version() == fusion.ABI_VERSION
+    monkeypatch.undo()
+    assert fusion.load() is not first and fusion.load() is fusion.load() and _lib.load() is lib
 
 
 def test_header_and_ctypes_struct_agree():

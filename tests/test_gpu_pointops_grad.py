@@ -153,7 +153,7 @@ def _group_grad(go_t, idx_t, out_t, gather=False):
     from unipre3d_amd import _lib, pointops
     b, c, n = out_t.shape
     total = idx_t.shape[1]
-    lib, s = pointops.load(), pointops._stream(out_t.device)
+    lib, s = pointops.load(), _lib.stream_ptr(out_t.device)
     if gather:
         rc = lib.u3d_gather_points_grad(b, c, n, total, _lib.ptr(go_t), _lib.ptr(idx_t), _lib.ptr(out_t), s)
     else:
@@ -166,7 +166,7 @@ def _interp_grad(go_t, idx_t, w_t, out_t):
     from unipre3d_amd import _lib, pointops
     b, c, m = out_t.shape
     rc = pointops.load().u3d_three_interpolate_grad(b, c, idx_t.shape[1], m, _lib.ptr(go_t), _lib.ptr(idx_t), _lib.ptr(w_t), _lib.ptr(out_t),
-                                                    pointops._stream(out_t.device))
+                                                    _lib.stream_ptr(out_t.device))
     assert rc == 0
 
 

@@ -1,4 +1,5 @@
-"""ctypes binding of libunipre3d_rasterizer.so (the C-ABI declared in include/unipre3d_rasterizer.h).
+"""ctypes binding of libunipre3d_rasterizer.so (the C-ABI declared in include/unipre3d_rasterizer.h), and the loader and call helpers
+every native library of the package is bound through (`open_library`, `check`, `ptr`, `stream_ptr`, `on_device`).
 
 The product path has NO CPU or PyTorch fallback: if the HIP library is missing or cannot be loaded,
 `load()` raises.  `import torch` must precede the dlopen so that the library's libamdhip64.so.7
@@ -22,10 +23,6 @@ CSRC = os.path.join(_HERE, "csrc")
 ABI_VERSION = 5   # include/unipre3d_rasterizer.h: U3D_ABI_VERSION
 FLAG_PREFILTERED, FLAG_ANTIALIASING, FLAG_DEBUG, FLAG_EXACT_AA_GRAD, FLAG_STATS, FLAG_ACC_CLEAN, FLAG_SPARSE_BWD = 1, 2, 4, 8, 16, 32, 64
 
-EXPORTS = ("u3d_abi_version", "u3d_error_string", "u3d_scratch_query", "u3d_rasterize_forward",
-           "u3d_rasterize_backward", "u3d_mark_visible", "u3d_profile_begin", "u3d_profile_end",
-           "u3d_render_loss_forward", "u3d_render_loss_backward", "u3d_render_loss_step",
-           "u3d_render_loss_step_forward", "u3d_render_loss_step_backward", "u3d_render_view_forward", "u3d_render_view_backward")
 PROFILE_KINDS = ("preprocess_fwd", "depth_sort", "render_fwd", "render_bwd", "preprocess_bwd", "render_fb")
 
 
@@ -68,57 +65,94 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
-_lib = None
+_handles = {}
 
 
-def load() -> ctypes.CDLL:
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"{LIB_PATH} is missing: the MI355X rasterizer has no fallback path. Build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C unipre3d_amd/csrc`.")
-    lib = ctypes.CDLL(LIB_PATH)
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
-    lib.u3d_abi_version.restype = ctypes.c_int
-    lib.u3d_error_string.restype = ctypes.c_char_p
-    lib.u3d_error_string.argtypes = [ctypes.c_int]
-    lib.u3d_scratch_query.restype = ctypes.c_int
-    lib.u3d_scratch_query.argtypes = [ctypes.POINTER(RasterDesc), ctypes.POINTER(ScratchSizes)]
-    lib.u3d_rasterize_forward.restype = ctypes.c_int
-    lib.u3d_rasterize_forward.argtypes = [ctypes.POINTER(RasterDesc)] + [vp] * 18
-    lib.u3d_rasterize_backward.restype = ctypes.c_int
-    lib.u3d_rasterize_backward.argtypes = [ctypes.POINTER(RasterDesc)] + [vp] * 27
-    lib.u3d_mark_visible.restype = ctypes.c_int
-    lib.u3d_mark_visible.argtypes = [i32, vp, vp, vp, vp, vp]
-    lib.u3d_render_loss_forward.restype = ctypes.c_int
-    lib.u3d_render_loss_forward.argtypes = [ctypes.POINTER(RasterDesc), ctypes.POINTER(HeadDesc), ctypes.POINTER(LossDesc)] + [vp] * 15
-    lib.u3d_render_loss_backward.restype = ctypes.c_int
-    lib.u3d_render_loss_backward.argtypes = [ctypes.POINTER(RasterDesc), ctypes.POINTER(HeadDesc), ctypes.POINTER(LossDesc)] + [vp] * 18
-    lib.u3d_render_loss_step.restype = ctypes.c_int
-    lib.u3d_render_loss_step.argtypes = [ctypes.POINTER(RasterDesc), ctypes.POINTER(HeadDesc), ctypes.POINTER(LossDesc)] + [vp] * 16
-    lib.u3d_render_loss_step_forward.restype = ctypes.c_int
-    lib.u3d_render_loss_step_forward.argtypes = [ctypes.POINTER(RasterDesc), ctypes.POINTER(HeadDesc), ctypes.POINTER(LossDesc)] + [vp] * 16
-    lib.u3d_render_loss_step_backward.restype = ctypes.c_int
-    lib.u3d_render_loss_step_backward.argtypes = [ctypes.POINTER(RasterDesc), ctypes.POINTER(HeadDesc)] + [vp] * 13
-    lib.u3d_render_view_forward.restype = ctypes.c_int
-    lib.u3d_render_view_forward.argtypes = [ctypes.POINTER(RasterDesc)] + [vp] * 17
-    lib.u3d_render_view_backward.restype = ctypes.c_int
-    lib.u3d_render_view_backward.argtypes = [ctypes.POINTER(RasterDesc)] + [vp] * 24
-    lib.u3d_profile_begin.restype = ctypes.c_int
-    lib.u3d_profile_begin.argtypes = [i32]
-    lib.u3d_profile_end.restype = ctypes.c_int
-    lib.u3d_profile_end.argtypes = [vp, vp]
-    if lib.u3d_abi_version() != ABI_VERSION:
-        raise RuntimeError("libunipre3d_rasterizer.so ABI version mismatch; rebuild")
-    _lib = lib
+def open_library(file_name: str, signatures: dict, abi=None) -> ctypes.CDLL:
+    """The library `file_name` of LIB_DIR, opened once and bound from its table: `signatures` maps every exported name to
+    (restype, argtypes) and both are set for every entry; `abi` = (symbol, expected) is checked where the library exports a version.
+    No fallback: a missing file raises."""
+    key = (LIB_DIR, file_name)
+    lib = _handles.get(key)
+    if lib is None:
+        path = os.path.join(LIB_DIR, file_name)
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is missing (no fallback): run `make -C unipre3d_amd/csrc`")
+        lib = ctypes.CDLL(path)
+        for name, (restype, argtypes) in signatures.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, list(argtypes)
+        if abi is not None:
+            found = getattr(lib, abi[0])()
+            if found != abi[1]:
+                raise RuntimeError(f"{path}: ABI {found}, this module binds ABI {abi[1]}: rebuild (`make -C unipre3d_amd/csrc`)")
+        _handles[key] = lib
     return lib
 
 
-def check(code: int, what: str) -> None:
+_vp, _int, _i32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int32
+_desc, _head, _loss = ctypes.POINTER(RasterDesc), ctypes.POINTER(HeadDesc), ctypes.POINTER(LossDesc)
+SIGNATURES = {   # include/unipre3d_rasterizer.h
+    "u3d_abi_version": (_int, []),
+    "u3d_error_string": (ctypes.c_char_p, [_int]),
+    "u3d_scratch_query": (_int, [_desc, ctypes.POINTER(ScratchSizes)]),
+    "u3d_rasterize_forward": (_int, [_desc] + [_vp] * 18),
+    "u3d_rasterize_backward": (_int, [_desc] + [_vp] * 27),
+    "u3d_render_loss_forward": (_int, [_desc, _head, _loss] + [_vp] * 15),
+    "u3d_render_loss_backward": (_int, [_desc, _head, _loss] + [_vp] * 18),
+    "u3d_render_loss_step": (_int, [_desc, _head, _loss] + [_vp] * 16),
+    "u3d_render_loss_step_forward": (_int, [_desc, _head, _loss] + [_vp] * 16),
+    "u3d_render_loss_step_backward": (_int, [_desc, _head] + [_vp] * 13),
+    "u3d_render_view_forward": (_int, [_desc] + [_vp] * 17),
+    "u3d_render_view_backward": (_int, [_desc] + [_vp] * 24),
+    "u3d_mark_visible": (_int, [_i32, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_profile_begin": (_int, [_i32]),
+    "u3d_profile_end": (_int, [_vp, _vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+
+
+def load() -> ctypes.CDLL:
+    return open_library("libunipre3d_rasterizer.so", SIGNATURES, ("u3d_abi_version", ABI_VERSION))
+
+
+def check(code: int, what: str, named: bool = True) -> None:
+    """Raises on a non-zero return code.  The rasterizer names its codes (u3d_error_string); the other libraries export no such
+    table and pass named=False."""
     if code != 0:
-        raise RuntimeError(f"{what} failed: {load().u3d_error_string(code).decode()} (code {code})")
+        if named:
+            raise RuntimeError(f"{what} failed: {load().u3d_error_string(code).decode()} (code {code})")
+        raise RuntimeError(f"{what} failed with code {code}")
+
+
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def stream_ptr(dev=None):
+    """torch's CURRENT stream on the current device as a hipStream_t (the raw-handle query costs ~0.3 us, the Stream object
+    route ~10 us per call).  The kernels are launched on the calling thread's current HIP device, so tensors on another
+    device are refused instead of being launched against the wrong queue."""
+    cur = torch.cuda.current_device()
+    if dev is not None and dev.index is not None and dev.index != cur:
+        raise RuntimeError(f"tensors live on cuda:{dev.index} but the current device is cuda:{cur}; "
+                           f"call under torch.cuda.device({dev.index}) (one process per GPU sets it once)")
+    if _raw_stream is not None:
+        return ctypes.c_void_p(_raw_stream(cur))
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def on_device(module_name: str, *tensors):
+    """The one HIP device the tensors (None entries skipped) live on; anything else raises -- there is no CPU path."""
+    dev = None
+    for t in tensors:
+        if t is None:
+            continue
+        if t.device.type != "cuda":
+            raise RuntimeError(f"unipre3d_amd.{module_name} needs tensors on a HIP device; there is no CPU fallback")
+        if dev is not None and t.device != dev:
+            raise RuntimeError(f"unipre3d_amd.{module_name}: tensors on different devices ({dev}, {t.device})")
+        dev = t.device
+    return dev
 
 
 def ptr(t) -> ctypes.c_void_p:

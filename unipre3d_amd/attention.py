@@ -13,54 +13,26 @@ import os
 import torch
 
 from . import _lib
+from ._lib import check, on_device, stream_ptr
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_attention.so")
-EXPORTS = ("u3d_attn_abi_version", "u3d_attn_varlen_fwd", "u3d_attn_varlen_bwd", "u3d_segment_csr_fwd", "u3d_segment_csr_bwd")
 ABI_VERSION = 1
 MAX_SEQLEN = 1024
 HEAD_DIM = 16
-_at = None
+
+_i, _f, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+SIGNATURES = {   # include/unipre3d_attention.h (the segment_csr pair is scatter.py's)
+    "u3d_attn_abi_version": (_i, []),
+    "u3d_attn_varlen_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "u3d_attn_varlen_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "u3d_segment_csr_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "u3d_segment_csr_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
-    global _at
-    if _at is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing (no fallback): run `make -C unipre3d_amd/csrc`")
-        lib = ctypes.CDLL(LIB_PATH)
-        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        lib.u3d_attn_abi_version.argtypes = []
-        lib.u3d_attn_varlen_fwd.argtypes = [vp, vp, vp, vp, i, i, i, i, i, f, vp]
-        lib.u3d_attn_varlen_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, f, vp]
-        lib.u3d_segment_csr_fwd.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
-        lib.u3d_segment_csr_bwd.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
-        for n in EXPORTS:
-            getattr(lib, n).restype = ctypes.c_int
-        if lib.u3d_attn_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH}: ABI {lib.u3d_attn_abi_version()}, this module binds ABI {ABI_VERSION}: rebuild")
-        _at = lib
-    return _at
-
-
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with code {rc}")
-
-
-def _on_device(what, *ts):
-    dev = None
-    for t in ts:
-        if t.device.type != "cuda":
-            raise RuntimeError(f"unipre3d_amd.{what} needs tensors on a HIP device; there is no CPU fallback")
-        if dev is not None and t.device != dev:
-            raise RuntimeError(f"unipre3d_amd.{what}: tensors on different devices ({dev}, {t.device})")
-        dev = t.device
-    return dev
-
-
-def _stream(dev):
-    from .rasterizer import _stream_ptr
-    return _stream_ptr(dev)
+    return _lib.open_library("libunipre3d_attention.so", SIGNATURES, ("u3d_attn_abi_version", ABI_VERSION))
 
 
 class _VarlenAttention(torch.autograd.Function):
@@ -71,8 +43,8 @@ class _VarlenAttention(torch.autograd.Function):
         out = torch.empty(T, H, D, dtype=torch.float16, device=qkv.device)
         lse = torch.empty(H, T, dtype=torch.float32, device=qkv.device)
         if T > 0:
-            _check(load().u3d_attn_varlen_fwd(_lib.ptr(qkv), _lib.ptr(cu_seqlens), _lib.ptr(out), _lib.ptr(lse), T, S, H, D, max_seqlen,
-                                              softmax_scale, _stream(qkv.device)), "u3d_attn_varlen_fwd")
+            check(load().u3d_attn_varlen_fwd(_lib.ptr(qkv), _lib.ptr(cu_seqlens), _lib.ptr(out), _lib.ptr(lse), T, S, H, D, max_seqlen,
+                                             softmax_scale, stream_ptr(qkv.device)), "u3d_attn_varlen_fwd", named=False)
         ctx.save_for_backward(qkv, cu_seqlens, out, lse)
         ctx.args = (max_seqlen, softmax_scale)
         return out
@@ -85,9 +57,9 @@ class _VarlenAttention(torch.autograd.Function):
         dout = dout.to(torch.float16).contiguous()
         dqkv = torch.empty_like(qkv)
         if T > 0:
-            _check(load().u3d_attn_varlen_bwd(_lib.ptr(qkv), _lib.ptr(cu_seqlens), _lib.ptr(out), _lib.ptr(dout), _lib.ptr(lse),
-                                              _lib.ptr(dqkv), T, cu_seqlens.numel() - 1, H, D, max_seqlen, softmax_scale,
-                                              _stream(qkv.device)), "u3d_attn_varlen_bwd")
+            check(load().u3d_attn_varlen_bwd(_lib.ptr(qkv), _lib.ptr(cu_seqlens), _lib.ptr(out), _lib.ptr(dout), _lib.ptr(lse),
+                                             _lib.ptr(dqkv), T, cu_seqlens.numel() - 1, H, D, max_seqlen, softmax_scale,
+                                             stream_ptr(qkv.device)), "u3d_attn_varlen_bwd", named=False)
         return dqkv, None, None, None
 
 
@@ -114,7 +86,7 @@ def flash_attn_varlen_qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0,
     if unknown:
         raise TypeError(f"flash_attn_varlen_qkvpacked_func: unexpected arguments {sorted(unknown)}")
     load()
-    dev = _on_device("attention", qkv, cu_seqlens)
+    dev = on_device("attention", qkv, cu_seqlens)
     if qkv.dim() != 4 or qkv.shape[1] != 3:
         raise ValueError(f"qkv: expected (T, 3, H, D), got {tuple(qkv.shape)}")
     if qkv.dtype != torch.float16:

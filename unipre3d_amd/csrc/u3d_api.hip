@@ -47,7 +47,7 @@ int check_desc(const u3d_raster_desc* d) {
   if (!(d->tanfovx > 0.f) || !(d->tanfovy > 0.f)) return U3D_ERR_INVALID_ARGUMENT;
   // the launchers index views, tiles and (view, Gaussian) pairs with 32-bit integers: refuse shapes whose products leave them
   const long long NV = (long long)d->n_items * d->views_per_item;
-  const long long T = (long long)((d->image_width + U3D_TILE - 1) / U3D_TILE) * ((d->image_height + U3D_TILE - 1) / U3D_TILE);
+  const long long T = (long long)u3d_tile_count(*d);
   if (NV >= (1ll << 31) || T >= (1ll << 31) || NV * T >= (1ll << 31)) return U3D_ERR_UNSUPPORTED;
   const long long SP = d->total_P > 0 ? (long long)d->total_P : (long long)d->n_items * d->P;   // Gaussians in the call
   if (SP >= (1ll << 31)) return U3D_ERR_UNSUPPORTED;
@@ -157,6 +157,97 @@ int finish(const u3d_raster_desc* d, hipStream_t s) {
   return U3D_OK;
 }
 
+// ---- the launch frames the entry points share ---------------------------------------------------
+struct Cameras { const float* view; const float* proj; const float* campos; };   // [n_views][16], [n_views][16], [n_views][3]
+
+// u3d_render_view_*: SH coefficient 0 is read from features_dc, coefficients 1.. from features_rest
+U3DSource split_sh_source(const u3d_raster_desc& d, const float* means3D, const float* features_dc, const float* features_rest,
+                          const float* opacities, const float* scales, const float* rotations) {
+  U3DSource src = plain_source(d, means3D, features_dc, nullptr, opacities, scales, rotations, nullptr);
+  src.s_shs = 3;
+  src.shs_rest = features_rest; src.s_shs_rest = (d.sh_coeffs - 1) * 3;
+  return src;
+}
+
+// head_source for a forward.  The object-level head (mode 1) needs the across-point quaternion norms: preprocess_fwd computes them
+// itself when one workgroup holds the whole set (P <= 256), else they are launched here; both clear `qdot_zero` (may be null).
+U3DSource head_source_forward(const u3d_raster_desc& d, const u3d_head_desc& h, const float* head_out, const float* center,
+                              const U3DFused& f, float* qdot_zero, hipStream_t s) {
+  U3DSource src = head_source(d, h, head_out, center, f.qnorm);
+  if (h.mode == 1) {
+    if (u3d_preprocess_sorts(d)) { src.qnorm_out = f.qnorm; src.qdot_zero = qdot_zero; }
+    else u3d_launch_quat_norms(d, head_out + 7, h.channels, f.qnorm, qdot_zero, s);
+  }
+  return src;
+}
+
+// d(head_out) as the gradient sink: the channels of head_source; qdot collects the across-point quaternion term
+U3DGradSink head_sink(float* d_head_out, float* qdot) {
+  U3DGradSink sink{};
+  sink.means = d_head_out; sink.opac = d_head_out + 3; sink.scales = d_head_out + 4; sink.rots = d_head_out + 7;
+  sink.shs = d_head_out + 11; sink.qdot = qdot;
+  return sink;
+}
+
+// backward_scratch = [f64 gradient accumulators, acc_bytes][per-tile partial rows]
+struct BackwardScratch { double* acc; float* part; };
+BackwardScratch split_backward_scratch(void* backward_scratch, const U3DLayout& L) {
+  return BackwardScratch{(double*)backward_scratch, (float*)((char*)backward_scratch + L.acc_bytes)};
+}
+
+// What opens every forward: the STATS counters, and n_vis of a call without Gaussians (the sort writes n_vis whenever P > 0)
+void forward_clears(const u3d_raster_desc& d, const U3DBuffers& b, hipStream_t s) {
+  const size_t NV = (size_t)d.n_items * d.views_per_item;
+  if (d.flags & U3D_FLAG_STATS) (void)hipMemsetAsync(b.num_rendered, 0, sizeof(uint32_t) * NV, s);
+  if (d.P == 0) (void)hipMemsetAsync(b.n_vis, 0, sizeof(uint32_t) * NV, s);
+}
+
+// Projection (kind 0) and, unless the projection orders the views itself, the depth sort (kind 1).  acc_zero: accumulators the
+// projection clears per projected pair (or null); visibility: radii > 0 per pair (or null).
+void project_and_sort(const u3d_raster_desc& d, const U3DBuffers& b, const U3DSource& src, const Cameras& cam, int32_t* radii,
+                      double* acc_zero, uint8_t* visibility, hipStream_t s) {
+  {
+    ProfScope ps(0, s);
+    u3d_launch_preprocess_fwd(d, b, src, cam.view, cam.proj, cam.campos, radii, acc_zero, s, visibility);
+  }
+  if (!u3d_preprocess_sorts(d)) {
+    ProfScope ps(1, s);
+    u3d_launch_depth_sort(d, b, radii, s);
+  }
+}
+
+void render_forward(const u3d_raster_desc& d, const U3DBuffers& b, const float* bg, float* out_color, float* out_invdepth,
+                    const U3DLoss& loss, hipStream_t s) {
+  ProfScope ps(2, s);
+  u3d_launch_render_fwd(d, b, bg, out_color, out_invdepth, loss, s);
+}
+
+// The operator's forward frame (u3d_rasterize_forward, u3d_render_view_forward)
+void plain_forward(const u3d_raster_desc& d, const U3DBuffers& b, const U3DSource& src, const Cameras& cam, int32_t* radii,
+                   uint8_t* visibility, const float* bg, float* out_color, float* out_invdepth, hipStream_t s) {
+  forward_clears(d, b, s);
+  if (d.P > 0) project_and_sort(d, b, src, cam, radii, nullptr, visibility, s);
+  render_forward(d, b, bg, out_color, out_invdepth, U3DLoss{}, s);
+}
+
+// The operator's backward frame (u3d_rasterize_backward, u3d_render_view_backward).  U3D_FLAG_ACC_CLEAN: the caller keeps this
+// scratch between calls of this shape and vouches that the accumulators are zero: no memset node, one launch less per call of the
+// per-view route.  The projection backward always hands the accumulators it read back zeroed (only touched pairs were written).
+void plain_backward(const u3d_raster_desc& d, const U3DBuffers& b, const U3DLayout& L, void* backward_scratch, const U3DSource& src,
+                    const Cameras& cam, const int32_t* radii, const float* bg, const float* dL_dcolor, const float* dL_dinvdepth,
+                    const U3DGradSink& sink, hipStream_t s) {
+  const BackwardScratch w = split_backward_scratch(backward_scratch, L);
+  if (!(d.flags & U3D_FLAG_ACC_CLEAN)) (void)hipMemsetAsync(w.acc, 0, L.acc_bytes, s);
+  {
+    ProfScope ps(3, s);
+    u3d_launch_render_bwd(d, b, bg, dL_dcolor, dL_dinvdepth, nullptr, U3DLoss{}, w.acc, w.part, s);
+  }
+  {
+    ProfScope ps(4, s);
+    u3d_launch_preprocess_bwd(d, b, src, cam.view, cam.proj, cam.campos, radii, w.acc, sink, s, w.acc);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -210,23 +301,8 @@ int u3d_rasterize_forward(const u3d_raster_desc* desc, const float* bg, const fl
   if ((rc = validate_offsets(d, geom, s)) != U3D_OK) return rc;
   U3DBuffers b{};
   u3d_carve(d, geom, binning, image, &b);
-  if (d.flags & U3D_FLAG_STATS) (void)hipMemsetAsync(b.num_rendered, 0, sizeof(uint32_t) * NV, s);
-  if (d.P == 0) (void)hipMemsetAsync(b.n_vis, 0, sizeof(uint32_t) * NV, s);   // the sort writes n_vis whenever P > 0
-  if (d.P > 0) {
-    {
-      ProfScope ps(0, s);
-      u3d_launch_preprocess_fwd(d, b, plain_source(d, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp),
-                                viewmatrix, projmatrix, campos, radii, nullptr, s);
-    }
-    if (!u3d_preprocess_sorts(d)) {
-      ProfScope ps(1, s);
-      u3d_launch_depth_sort(d, b, radii, s);
-    }
-  }
-  {
-    ProfScope ps(2, s);
-    u3d_launch_render_fwd(d, b, bg, out_color, out_invdepth, U3DLoss{}, s);
-  }
+  plain_forward(d, b, plain_source(d, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp),
+                Cameras{viewmatrix, projmatrix, campos}, radii, nullptr, bg, out_color, out_invdepth, s);
   return finish(desc, s);
 }
 
@@ -254,26 +330,12 @@ int u3d_rasterize_backward(const u3d_raster_desc* desc, const float* bg, const f
   hipStream_t s = (hipStream_t)stream;
   U3DBuffers b{};
   const U3DLayout L = u3d_carve(d, (void*)geom, (void*)binning, (void*)image, &b);
-  double* acc = (double*)backward_scratch;
-  float* part = (float*)((char*)backward_scratch + L.acc_bytes);
-  // U3D_FLAG_ACC_CLEAN: the caller keeps this scratch between calls of this shape and vouches that the accumulators are zero
-  // (the previous call handed them back zeroed, see below): no memset node -- one launch less per call of the per-view route
-  const bool clean = (d.flags & U3D_FLAG_ACC_CLEAN) != 0;
-  if (!clean) (void)hipMemsetAsync(acc, 0, L.acc_bytes, s);
-  {
-    ProfScope ps(3, s);
-    u3d_launch_render_bwd(d, b, bg, dL_dcolor, dL_dinvdepth, nullptr, U3DLoss{}, acc, part, s);
-  }
-  {
-    ProfScope ps(4, s);
-    U3DGradSink sink{};
-    sink.means = dL_dmeans3D; sink.shs = shs ? dL_dshs : nullptr; sink.colors = dL_dcolors; sink.opac = dL_dopacity;
-    sink.scales = scales ? dL_dscales : nullptr; sink.rots = scales ? dL_drotations : nullptr; sink.cov = dL_dcov3D;
-    sink.means2D = dL_dmeans2D; sink.qdot = nullptr;
-    // (always hands the accumulators it read back zeroed: only the touched (view, Gaussian) pairs were ever written)
-    u3d_launch_preprocess_bwd(d, b, plain_source(d, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp),
-                              viewmatrix, projmatrix, campos, radii, acc, sink, s, acc);
-  }
+  U3DGradSink sink{};
+  sink.means = dL_dmeans3D; sink.shs = shs ? dL_dshs : nullptr; sink.colors = dL_dcolors; sink.opac = dL_dopacity;
+  sink.scales = scales ? dL_dscales : nullptr; sink.rots = scales ? dL_drotations : nullptr; sink.cov = dL_dcov3D;
+  sink.means2D = dL_dmeans2D;
+  plain_backward(d, b, L, backward_scratch, plain_source(d, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp),
+                 Cameras{viewmatrix, projmatrix, campos}, radii, bg, dL_dcolor, dL_dinvdepth, sink, s);
   return finish(desc, s);
 }
 
@@ -296,25 +358,8 @@ int u3d_render_view_forward(const u3d_raster_desc* desc, const float* bg, const 
   if ((rc = validate_offsets(d, geom, s)) != U3D_OK) return rc;
   U3DBuffers b{};
   u3d_carve(d, geom, binning, image, &b);
-  if (d.flags & U3D_FLAG_STATS) (void)hipMemsetAsync(b.num_rendered, 0, sizeof(uint32_t) * NV, s);
-  if (d.P == 0) (void)hipMemsetAsync(b.n_vis, 0, sizeof(uint32_t) * NV, s);
-  if (d.P > 0) {
-    U3DSource src = plain_source(d, means3D, features_dc, nullptr, opacities, scales, rotations, nullptr);
-    src.s_shs = 3;
-    src.shs_rest = features_rest; src.s_shs_rest = (d.sh_coeffs - 1) * 3;
-    {
-      ProfScope ps(0, s);
-      u3d_launch_preprocess_fwd(d, b, src, viewmatrix, projmatrix, campos, radii, nullptr, s, visibility);
-    }
-    if (!u3d_preprocess_sorts(d)) {
-      ProfScope ps(1, s);
-      u3d_launch_depth_sort(d, b, radii, s);
-    }
-  }
-  {
-    ProfScope ps(2, s);
-    u3d_launch_render_fwd(d, b, bg, out_color, nullptr, U3DLoss{}, s);
-  }
+  plain_forward(d, b, split_sh_source(d, means3D, features_dc, features_rest, opacities, scales, rotations),
+                Cameras{viewmatrix, projmatrix, campos}, radii, visibility, bg, out_color, nullptr, s);
   return finish(desc, s);
 }
 
@@ -338,23 +383,11 @@ int u3d_render_view_backward(const u3d_raster_desc* desc, const float* bg, const
   hipStream_t s = (hipStream_t)stream;
   U3DBuffers b{};
   const U3DLayout L = u3d_carve(d, (void*)geom, (void*)binning, (void*)image, &b);
-  double* acc = (double*)backward_scratch;
-  float* part = (float*)((char*)backward_scratch + L.acc_bytes);
-  if (!(d.flags & U3D_FLAG_ACC_CLEAN)) (void)hipMemsetAsync(acc, 0, L.acc_bytes, s);
-  {
-    ProfScope ps(3, s);
-    u3d_launch_render_bwd(d, b, bg, dL_dcolor, nullptr, nullptr, U3DLoss{}, acc, part, s);
-  }
-  {
-    ProfScope ps(4, s);
-    U3DSource src = plain_source(d, means3D, features_dc, nullptr, opacities, scales, rotations, nullptr);
-    src.s_shs = 3;
-    src.shs_rest = features_rest; src.s_shs_rest = (d.sh_coeffs - 1) * 3;
-    U3DGradSink sink{};
-    sink.means = dL_dmeans3D; sink.shs = dL_dfeatures_dc; sink.shs_rest = dL_dfeatures_rest; sink.opac = dL_dopacity;
-    sink.scales = dL_dscales; sink.rots = dL_drotations; sink.means2D = dL_dmeans2D;
-    u3d_launch_preprocess_bwd(d, b, src, viewmatrix, projmatrix, campos, radii, acc, sink, s, acc);
-  }
+  U3DGradSink sink{};
+  sink.means = dL_dmeans3D; sink.shs = dL_dfeatures_dc; sink.shs_rest = dL_dfeatures_rest; sink.opac = dL_dopacity;
+  sink.scales = dL_dscales; sink.rots = dL_drotations; sink.means2D = dL_dmeans2D;
+  plain_backward(d, b, L, backward_scratch, split_sh_source(d, means3D, features_dc, features_rest, opacities, scales, rotations),
+                 Cameras{viewmatrix, projmatrix, campos}, radii, bg, dL_dcolor, nullptr, sink, s);
   return finish(desc, s);
 }
 
@@ -377,27 +410,12 @@ int u3d_render_loss_forward(const u3d_raster_desc* desc, const u3d_head_desc* he
   u3d_carve(d, geom, binning, image, &b);
   U3DFused f{};
   u3d_carve_fused(d, fused, &f);
-  if (d.flags & U3D_FLAG_STATS) (void)hipMemsetAsync(b.num_rendered, 0, sizeof(uint32_t) * NV, s);
-  U3DSource src = head_source(d, *head, head_out, center, f.qnorm);
-  if (head->mode == 1) {
-    if (u3d_preprocess_sorts(d)) src.qnorm_out = f.qnorm;   // P <= 256: norms computed inside preprocess_fwd
-    else u3d_launch_quat_norms(d, head_out + 7, head->channels, f.qnorm, nullptr, s);
-  }
-  {
-    ProfScope ps(0, s);
-    u3d_launch_preprocess_fwd(d, b, src, viewmatrix, projmatrix, campos, radii, nullptr, s);
-  }
-  if (!u3d_preprocess_sorts(d)) {
-    ProfScope ps(1, s);
-    u3d_launch_depth_sort(d, b, radii, s);
-  }
-  const int T = ((d.image_width + U3D_TILE - 1) / U3D_TILE) * ((d.image_height + U3D_TILE - 1) / U3D_TILE);
+  forward_clears(d, b, s);
+  const U3DSource src = head_source_forward(d, *head, head_out, center, f, nullptr, s);
+  project_and_sort(d, b, src, Cameras{viewmatrix, projmatrix, campos}, radii, nullptr, nullptr, s);
   const U3DLoss L = make_loss(d, *loss, gt, f.partial, nullptr);
-  {
-    ProfScope ps(2, s);
-    u3d_launch_render_fwd(d, b, bg, out_color, nullptr, L, s);
-  }
-  u3d_launch_loss_reduce(NV * T, f.partial, L.inv_count, loss_out, s);
+  render_forward(d, b, bg, out_color, nullptr, L, s);
+  u3d_launch_loss_reduce(NV * (int)u3d_tile_count(d), f.partial, L.inv_count, loss_out, s);
   return finish(desc, s);
 }
 
@@ -420,25 +438,20 @@ int u3d_render_loss_backward(const u3d_raster_desc* desc, const u3d_head_desc* h
   const U3DLayout Lay = u3d_carve(d, (void*)geom, (void*)binning, (void*)image, &b);
   U3DFused f{};
   u3d_carve_fused(d, fused, &f);
-  double* acc = (double*)backward_scratch;
-  float* part = (float*)((char*)backward_scratch + Lay.acc_bytes);
-  (void)hipMemsetAsync(acc, 0, Lay.acc_bytes, s);
+  const BackwardScratch w = split_backward_scratch(backward_scratch, Lay);
+  (void)hipMemsetAsync(w.acc, 0, Lay.acc_bytes, s);
   (void)hipMemsetAsync(f.qdot, 0, sizeof(float) * 4 * d.n_items, s);
   const U3DLoss L = make_loss(d, *loss, gt, f.partial, dloss);
   {
     ProfScope ps(3, s);
-    u3d_launch_render_bwd(d, b, bg, dL_dcolor_extra, nullptr, out_color, L, acc, part, s);
+    u3d_launch_render_bwd(d, b, bg, dL_dcolor_extra, nullptr, out_color, L, w.acc, w.part, s);
   }
-  const int C = head->channels;
-  U3DGradSink sink{};
-  sink.means = d_head_out; sink.opac = d_head_out + 3; sink.scales = d_head_out + 4; sink.rots = d_head_out + 7;
-  sink.shs = d_head_out + 11; sink.colors = nullptr; sink.cov = nullptr; sink.means2D = nullptr; sink.qdot = f.qdot;
   {
     ProfScope ps(4, s);
     u3d_launch_preprocess_bwd(d, b, head_source(d, *head, head_out, center, f.qnorm), viewmatrix, projmatrix, campos, radii,
-                              acc, sink, s);
+                              w.acc, head_sink(d_head_out, f.qdot), s);
   }
-  if (head->mode == 1) u3d_launch_quat_fixup(d, head_out + 7, C, f.qnorm, f.qdot, d_head_out + 7, s);
+  if (head->mode == 1) u3d_launch_quat_fixup(d, head_out + 7, head->channels, f.qnorm, f.qdot, d_head_out + 7, s);
   return finish(desc, s);
 }
 
@@ -467,28 +480,17 @@ int u3d_render_loss_step_forward(const u3d_raster_desc* desc, const u3d_head_des
   const U3DLayout Lay = u3d_carve(d, geom, binning, nullptr, &b);
   U3DFused f{};
   u3d_carve_fused(d, fused, &f);
-  double* acc = (double*)backward_scratch;
-  float* part = (float*)((char*)backward_scratch + Lay.acc_bytes);
-  if (d.flags & U3D_FLAG_STATS) (void)hipMemsetAsync(b.num_rendered, 0, sizeof(uint32_t) * NV, s);
-  // no memset nodes: quat_norms clears qdot, preprocess_fwd clears the accumulators of the (view, Gaussian) it projects
-  U3DSource src = head_source(d, *head, head_out, center, f.qnorm);
-  if (head->mode == 1) {
-    if (u3d_preprocess_sorts(d)) { src.qnorm_out = f.qnorm; src.qdot_zero = f.qdot; }   // P <= 256: inside preprocess_fwd
-    else u3d_launch_quat_norms(d, head_out + 7, head->channels, f.qnorm, f.qdot, s);
-  }
-  {
-    ProfScope ps(0, s);
-    // (the accumulators are cleared per projected pair here unless the caller vouches for them, U3D_FLAG_ACC_CLEAN)
-    u3d_launch_preprocess_fwd(d, b, src, viewmatrix, projmatrix, campos, radii, (d.flags & U3D_FLAG_ACC_CLEAN) ? nullptr : acc, s);
-  }
-  if (!u3d_preprocess_sorts(d)) {
-    ProfScope ps(1, s);
-    u3d_launch_depth_sort(d, b, radii, s);
-  }
+  const BackwardScratch w = split_backward_scratch(backward_scratch, Lay);
+  forward_clears(d, b, s);
+  // no memset nodes: quat_norms clears qdot, preprocess_fwd clears the accumulators of the (view, Gaussian) it projects -- unless
+  // the caller vouches for them (U3D_FLAG_ACC_CLEAN)
+  const U3DSource src = head_source_forward(d, *head, head_out, center, f, f.qdot, s);
+  project_and_sort(d, b, src, Cameras{viewmatrix, projmatrix, campos}, radii, (d.flags & U3D_FLAG_ACC_CLEAN) ? nullptr : w.acc,
+                   nullptr, s);
   const U3DLoss L = make_loss(d, *loss, gt, f.partial, nullptr);
   {
     ProfScope ps(5, s);
-    u3d_launch_render_fb(d, b, bg, out_color, L, acc, part, loss_out, s, sparse ? d_head_out : nullptr,
+    u3d_launch_render_fb(d, b, bg, out_color, L, w.acc, w.part, loss_out, s, sparse ? d_head_out : nullptr,
                          sparse ? u3d_total_P(d) * (size_t)head->channels : 0, sparse);   // + partial reduce + loss reduce
   }
   return finish(desc, s);
@@ -513,14 +515,10 @@ int u3d_render_loss_step_backward(const u3d_raster_desc* desc, const u3d_head_de
   U3DFused f{};
   u3d_carve_fused(d, fused, &f);
   double* acc = (double*)backward_scratch;
-  const U3DSource src = head_source(d, *head, head_out, center, f.qnorm);
-  U3DGradSink sink{};
-  sink.means = d_head_out; sink.opac = d_head_out + 3; sink.scales = d_head_out + 4; sink.rots = d_head_out + 7;
-  sink.shs = d_head_out + 11; sink.colors = nullptr; sink.cov = nullptr; sink.means2D = nullptr; sink.qdot = f.qdot;
   {
-    ProfScope ps(4, s);
-    u3d_launch_preprocess_bwd(d, b, src, viewmatrix, projmatrix, campos, radii, acc, sink, s, acc, dloss,
-                              u3d_sparse_bwd(d, head->mode));   // reads, then re-zeroes, the touched accumulators
+    ProfScope ps(4, s);   // reads, then re-zeroes, the touched accumulators
+    u3d_launch_preprocess_bwd(d, b, head_source(d, *head, head_out, center, f.qnorm), viewmatrix, projmatrix, campos, radii, acc,
+                              head_sink(d_head_out, f.qdot), s, acc, dloss, u3d_sparse_bwd(d, head->mode));
   }
   if (head->mode == 1) u3d_launch_quat_fixup(d, head_out + 7, head->channels, f.qnorm, f.qdot, d_head_out + 7, s);
   return finish(desc, s);

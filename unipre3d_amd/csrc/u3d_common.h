@@ -74,6 +74,9 @@ struct U3DSpan {
 };
 static inline U3DSpan u3d_span(const u3d_raster_desc& d) { return U3DSpan{d.total_P > 0 ? d.item_offsets : nullptr, d.P, d.views_per_item}; }
 static inline size_t u3d_total_P(const u3d_raster_desc& d) { return d.total_P > 0 ? (size_t)d.total_P : (size_t)d.n_items * (size_t)d.P; }
+static inline size_t u3d_tile_count(const u3d_raster_desc& d) {   // tiles of one view
+  return (size_t)((d.image_width + U3D_TILE - 1) / U3D_TILE) * ((d.image_height + U3D_TILE - 1) / U3D_TILE);
+}
 #ifdef __HIPCC__
 __device__ __forceinline__ void u3d_set_span(const U3DSpan& s, int item, int& Pi, size_t& gbase) {
   // (a set never has more than desc.P Gaussians: a malformed prefix-sum table is truncated here, in every kernel alike, rather
@@ -168,7 +171,7 @@ struct U3DFused {
 };
 static inline size_t u3d_carve_fused(const u3d_raster_desc& d, void* base, U3DFused* f) {
   const size_t NV = (size_t)d.n_items * d.views_per_item;
-  const size_t T = (size_t)((d.image_width + U3D_TILE - 1) / U3D_TILE) * ((d.image_height + U3D_TILE - 1) / U3D_TILE);
+  const size_t T = u3d_tile_count(d);
   const size_t a = (((size_t)d.n_items * 4 * sizeof(float)) + 255) & ~(size_t)255;
   if (f) {
     f->qnorm = (float*)base;
@@ -233,14 +236,14 @@ static inline U3DLayout u3d_carve(const u3d_raster_desc& d, void* geom, void* bi
   char* im = (char*)image;
   CARVE(im, final_T, float, NP);
   CARVE(im, n_contrib, uint32_t, NP);
-  CARVE(im, tile_last, uint32_t, NV * (size_t)((d.image_width + U3D_TILE - 1) / U3D_TILE) * ((d.image_height + U3D_TILE - 1) / U3D_TILE));
+  CARVE(im, tile_last, uint32_t, NV * u3d_tile_count(d));
   L.image_bytes = o > 0 ? o : 256;
 #undef CARVE
   // f64 accumulators: global_atomic_add_f64 makes the cross-tile sum order-insensitive at fp32 output precision
   // + per-tile partials of the first 64 sorted positions: [NV*T][64][10] floats + [NV*T] row counts (see tile_backward)
   L.acc_bytes = u3d_align(sizeof(double) * U3D_NACC * (NG > 0 ? NG : 1));
   {
-    const size_t Tn = (size_t)((d.image_width + U3D_TILE - 1) / U3D_TILE) * ((d.image_height + U3D_TILE - 1) / U3D_TILE);
+    const size_t Tn = u3d_tile_count(d);
     // per tile: 64 sorted positions x 10 floats (the LDS rows as they are) + a compact count array
     L.backward_bytes = L.acc_bytes + u3d_align(sizeof(float) * U3D_PART_STRIDE * (NV * Tn > 0 ? NV * Tn : 1)) +
                        u3d_align(sizeof(uint32_t) * (NV * Tn > 0 ? NV * Tn : 1));

@@ -10,41 +10,29 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import check, on_device, stream_ptr
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_fusion.so")   # (U3D_LIB_DIRNAME: experiment builds, see _lib.py)
-EXPORTS = ("u3d_zbuffer_fusion_forward", "u3d_zbuffer_fusion_backward", "u3d_fusion_abi_version", "u3d_zbuffer_fusion_zbuf_bytes")
 ABI_VERSION = 2
-_fu = None
+
+_i, _f, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+SIGNATURES = {   # include/unipre3d_fusion.h
+    "u3d_fusion_abi_version": (_i, []),
+    "u3d_zbuffer_fusion_zbuf_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "u3d_zbuffer_fusion_forward": (_i, [_i, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_zbuffer_fusion_backward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
-    global _fu
-    if _fu is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing (no fallback): run `make -C unipre3d_amd/csrc`")
-        lib = ctypes.CDLL(LIB_PATH)
-        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        lib.u3d_zbuffer_fusion_forward.argtypes = [i, i, i, i, i, f, f, f, f, vp, vp, vp, vp, vp, vp]
-        lib.u3d_zbuffer_fusion_backward.argtypes = [i, i, i, i, i, vp, vp, vp, vp, vp]
-        lib.u3d_fusion_abi_version.argtypes = []
-        lib.u3d_zbuffer_fusion_zbuf_bytes.argtypes = [i, i, i]
-        for n in EXPORTS:
-            getattr(lib, n).restype = ctypes.c_int
-        lib.u3d_zbuffer_fusion_zbuf_bytes.restype = ctypes.c_size_t
-        if lib.u3d_fusion_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH}: ABI {lib.u3d_fusion_abi_version()}, this module binds ABI {ABI_VERSION}: rebuild (`make -C unipre3d_amd/csrc`)")
-        _fu = lib
-    return _fu
+    return _lib.open_library("libunipre3d_fusion.so", SIGNATURES, ("u3d_fusion_abi_version", ABI_VERSION))
 
 
 class _ZBufferGather(torch.autograd.Function):
     @staticmethod
     def forward(ctx, camera_points, image_features, fx, fy, cx, cy):
-        if camera_points.device.type != "cuda":
-            raise RuntimeError("unipre3d_amd.fusion needs tensors on a HIP device; there is no CPU fallback")
-        if image_features.device != camera_points.device:
-            raise RuntimeError(f"unipre3d_amd.fusion: tensors on different devices ({camera_points.device}, {image_features.device})")
-        from .rasterizer import _stream_ptr
+        dev = on_device("fusion", camera_points, image_features)
         B, N, _ = camera_points.shape
         _, C, H, W = image_features.shape
         cp, feat = camera_points.contiguous().float(), image_features.contiguous().float()
@@ -53,9 +41,8 @@ class _ZBufferGather(torch.autograd.Function):
         # winner table: (depth bits << 32 | first winner) per pixel + the "empty pixel" bitmap behind it
         zbuf = torch.empty((load().u3d_zbuffer_fusion_zbuf_bytes(B, H, W) + 7) // 8, dtype=torch.int64, device=cp.device)
         rc = load().u3d_zbuffer_fusion_forward(B, N, C, H, W, fx, fy, cx, cy, _lib.ptr(cp), _lib.ptr(feat), _lib.ptr(mapped),
-                                               _lib.ptr(sel), _lib.ptr(zbuf), _stream_ptr(cp.device))
-        if rc != 0:
-            raise RuntimeError(f"u3d_zbuffer_fusion_forward failed with code {rc}")
+                                               _lib.ptr(sel), _lib.ptr(zbuf), stream_ptr(dev))
+        check(rc, "u3d_zbuffer_fusion_forward", named=False)
         ctx.save_for_backward(sel, zbuf)
         ctx.shape = (B, N, C, H, W)
         ctx.mark_non_differentiable(sel)
@@ -68,10 +55,8 @@ class _ZBufferGather(torch.autograd.Function):
         # gather form: the kernel writes every element of the (B,C,H,W) gradient exactly once (no zero-fill + scatter)
         grad_feat = torch.empty(B, C, H, W, dtype=torch.float32, device=sel.device)
         g = grad_mapped.contiguous().float()
-        from .rasterizer import _stream_ptr
-        rc = load().u3d_zbuffer_fusion_backward(B, N, C, H, W, _lib.ptr(g), _lib.ptr(sel), _lib.ptr(zbuf), _lib.ptr(grad_feat), _stream_ptr(sel.device))
-        if rc != 0:
-            raise RuntimeError(f"u3d_zbuffer_fusion_backward failed with code {rc}")
+        rc = load().u3d_zbuffer_fusion_backward(B, N, C, H, W, _lib.ptr(g), _lib.ptr(sel), _lib.ptr(zbuf), _lib.ptr(grad_feat), stream_ptr(sel.device))
+        check(rc, "u3d_zbuffer_fusion_backward", named=False)
         return None, grad_feat, None, None, None, None
 
 

@@ -28,27 +28,22 @@ from typing import Iterable
 import torch
 
 from . import _lib
+from ._lib import check, stream_ptr
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_gradclip.so")   # (U3D_LIB_DIRNAME: experiment builds, see _lib.py)
-EXPORTS = ("u3d_gradclip_stats", "u3d_gradclip_finalize", "u3d_gradclip_scale")
 GC_CHUNK = 65536
-_gc = None
+
+_i32, _vp = ctypes.c_int32, ctypes.c_void_p
+SIGNATURES = {   # include/unipre3d_gradclip.h
+    "u3d_gradclip_stats": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "u3d_gradclip_finalize": (ctypes.c_int, [_vp, _i32, ctypes.c_float, _vp, _vp]),
+    "u3d_gradclip_scale": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
-    global _gc
-    if _gc is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing (no fallback on a HIP device): run `make -C unipre3d_amd/csrc`")
-        lib = ctypes.CDLL(LIB_PATH)
-        vp, i32 = ctypes.c_void_p, ctypes.c_int32
-        lib.u3d_gradclip_stats.argtypes = [vp, vp, vp, i32, i32, vp, vp]
-        lib.u3d_gradclip_finalize.argtypes = [vp, i32, ctypes.c_float, vp, vp]
-        lib.u3d_gradclip_scale.argtypes = [vp, vp, vp, i32, i32, vp, vp]
-        for n in EXPORTS:
-            getattr(lib, n).restype = ctypes.c_int
-        _gc = lib
-    return _gc
+    return _lib.open_library("libunipre3d_gradclip.so", SIGNATURES)
 
 
 class _Table:
@@ -138,11 +133,10 @@ def _scale_rest(rest, t):
 
 
 def _launch_stats(grads, max_norm):
-    from .rasterizer import _stream_ptr
     dev, fast, rest = _split(grads)
     if dev.type != "cuda":
         raise RuntimeError("unipre3d_amd.gradcheck: the HIP path needs gradients on a HIP device")
-    lib, t, s = load(), _table_for(fast, dev), _stream_ptr(dev)
+    lib, t, s = load(), _table_for(fast, dev), stream_ptr(dev)
     rc = 0
     if fast:
         rc = lib.u3d_gradclip_stats(t.ptrs.data_ptr(), t.numel.data_ptr(), t.first.data_ptr(), t.n, t.n_chunks, t.partials.data_ptr(), s)
@@ -150,8 +144,7 @@ def _launch_stats(grads, max_norm):
         _rest_record(rest, dev, t.partials, t.n_chunks)          # (the table keeps one spare record for them)
     if rc == 0:
         rc = lib.u3d_gradclip_finalize(t.partials.data_ptr(), t.n_chunks + (1 if rest else 0), float(max_norm), t.state.data_ptr(), s)
-    if rc != 0:
-        raise RuntimeError(f"u3d_gradclip_stats / _finalize failed with code {rc}")
+    check(rc, "u3d_gradclip_stats / _finalize", named=False)
     return lib, t, s, rest
 
 
@@ -159,8 +152,7 @@ def _launch_scale(lib, t, s, rest=()):
     rc = 0
     if t.n:
         rc = lib.u3d_gradclip_scale(t.ptrs.data_ptr(), t.numel.data_ptr(), t.first.data_ptr(), t.n, t.n_chunks, t.state.data_ptr(), s)
-    if rc != 0:
-        raise RuntimeError(f"u3d_gradclip_scale failed with code {rc}")
+    check(rc, "u3d_gradclip_scale", named=False)
     if rest:
         _scale_rest(rest, t)
 

@@ -19,62 +19,29 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import check, on_device, stream_ptr
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_pointfusion.so")
-EXPORTS = ("u3d_pointfusion_abi_version", "u3d_pointfusion_scratch_bytes", "u3d_pointfusion_minmax", "u3d_pointfusion_compact",
-           "u3d_pointfusion_voxelize", "u3d_pointfusion_pick", "u3d_pointfusion_inverse", "u3d_pointfusion_gather_forward",
-           "u3d_pointfusion_gather_backward")
 ABI_VERSION = 1
 MODES = {"train": 0, "test": 1}
-_pf = None
+
+_i, _f, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+SIGNATURES = {   # include/unipre3d_pointfusion.h
+    "u3d_pointfusion_abi_version": (_i, []),
+    "u3d_pointfusion_scratch_bytes": (ctypes.c_size_t, [_i, _i]),
+    "u3d_pointfusion_minmax": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_pointfusion_compact": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_pointfusion_voxelize": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
+    "u3d_pointfusion_pick": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_pointfusion_inverse": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_pointfusion_gather_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_pointfusion_gather_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
-    global _pf
-    if _pf is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing (no fallback): run `make -C unipre3d_amd/csrc`")
-        lib = ctypes.CDLL(LIB_PATH)
-        vp, i, f, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_uint64
-        lib.u3d_pointfusion_abi_version.argtypes = []
-        lib.u3d_pointfusion_scratch_bytes.argtypes = [i, i]
-        lib.u3d_pointfusion_minmax.argtypes = [i, i, vp, vp, vp, vp]
-        lib.u3d_pointfusion_compact.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
-        lib.u3d_pointfusion_voxelize.argtypes = [i, i, i, vp, vp, vp, i, f, vp, vp, vp, vp]
-        lib.u3d_pointfusion_pick.argtypes = [i, i, i, vp, vp, vp, vp, i, f, i, i, vp, u64, vp, vp, vp, vp, vp, vp, vp]
-        lib.u3d_pointfusion_inverse.argtypes = [i, i, i, vp, vp, vp, vp, vp]
-        lib.u3d_pointfusion_gather_forward.argtypes = [i, i, i, vp, vp, vp, vp]
-        lib.u3d_pointfusion_gather_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, vp]
-        for n in EXPORTS:
-            getattr(lib, n).restype = ctypes.c_int
-        lib.u3d_pointfusion_scratch_bytes.restype = ctypes.c_size_t
-        if lib.u3d_pointfusion_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH}: ABI {lib.u3d_pointfusion_abi_version()}, this module binds ABI {ABI_VERSION}: rebuild")
-        _pf = lib
-    return _pf
-
-
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with code {rc}")
-
-
-def _on_device(*ts):
-    dev = None
-    for t in ts:
-        if t is None:
-            continue
-        if t.device.type != "cuda":
-            raise RuntimeError("unipre3d_amd.pointfusion needs tensors on a HIP device; there is no CPU fallback")
-        if dev is not None and t.device != dev:
-            raise RuntimeError(f"unipre3d_amd.pointfusion: tensors on different devices ({dev}, {t.device})")
-        dev = t.device
-    return dev
-
-
-def _stream(dev):
-    from .rasterizer import _stream_ptr
-    return _stream_ptr(dev)
+    return _lib.open_library("libunipre3d_pointfusion.so", SIGNATURES, ("u3d_pointfusion_abi_version", ABI_VERSION))
 
 
 def _seed(generator=None) -> int:
@@ -94,9 +61,9 @@ def _min_rows(min_coord, S, dev):
 def _voxelize(coord, grid_size, mins, min_stride, S, offsets, n_max, n, scratch, meta):
     dev = coord.device
     voxel_offsets = torch.empty(S + 1, dtype=torch.int32, device=dev)
-    _check(load().u3d_pointfusion_voxelize(n_max, n, S, _lib.ptr(offsets), _lib.ptr(coord), _lib.ptr(mins), min_stride,
-                                           float(np.float32(grid_size)), _lib.ptr(meta), _lib.ptr(voxel_offsets), _lib.ptr(scratch),
-                                           _stream(dev)), "u3d_pointfusion_voxelize")
+    check(load().u3d_pointfusion_voxelize(n_max, n, S, _lib.ptr(offsets), _lib.ptr(coord), _lib.ptr(mins), min_stride,
+                                          float(np.float32(grid_size)), _lib.ptr(meta), _lib.ptr(voxel_offsets), _lib.ptr(scratch),
+                                          stream_ptr(dev)), "u3d_pointfusion_voxelize", named=False)
     return voxel_offsets
 
 
@@ -113,10 +80,10 @@ def _pick(M, n_max, S, offsets, voxel_offsets, coord, mins, min_stride, grid_siz
     out_coord = torch.empty(M, 3, dtype=torch.float32, device=dev)
     grid = torch.empty(M, 3, dtype=torch.int64, device=dev)
     src = torch.empty(M, dtype=torch.int32, device=dev) if src_map is not None else None
-    _check(load().u3d_pointfusion_pick(M, n_max, S, _lib.ptr(offsets), _lib.ptr(voxel_offsets), _lib.ptr(coord), _lib.ptr(mins),
-                                       min_stride, float(np.float32(grid_size)), MODES[mode], int(part), _lib.ptr(draws), seed,
-                                       _lib.ptr(src_map), _lib.ptr(index), _lib.ptr(out_coord), _lib.ptr(grid), _lib.ptr(src),
-                                       _lib.ptr(scratch), _stream(dev)), "u3d_pointfusion_pick")
+    check(load().u3d_pointfusion_pick(M, n_max, S, _lib.ptr(offsets), _lib.ptr(voxel_offsets), _lib.ptr(coord), _lib.ptr(mins),
+                                      min_stride, float(np.float32(grid_size)), MODES[mode], int(part), _lib.ptr(draws), seed,
+                                      _lib.ptr(src_map), _lib.ptr(index), _lib.ptr(out_coord), _lib.ptr(grid), _lib.ptr(src),
+                                      _lib.ptr(scratch), stream_ptr(dev)), "u3d_pointfusion_pick", named=False)
     return index, out_coord, grid, src
 
 
@@ -130,7 +97,7 @@ def grid_sample(coord, grid_size=0.02, min_coord=None, mode="train", draws=None,
     group equals a single-set call.  Returns a dict: index (M,) int64 (set-local point index of each voxel's pick), coord (M,3),
     grid_coord (M,3) int64, voxel_sizes (S,) int64 (voxels per set), max_count (int, largest voxel), inverse (N,) int64 set-local
     voxel of each point when return_inverse."""
-    dev = _on_device(coord)   # (min_coord may be a host value, as the reference's numpy one)
+    dev = on_device("pointfusion", coord)   # (min_coord may be a host value, as the reference's numpy one)
     coord = coord.detach().contiguous()
     if coord.dtype != torch.float32 or coord.dim() != 2 or coord.shape[1] != 3:
         raise ValueError(f"coord: expected (N,3) float32, got {tuple(coord.shape)} {coord.dtype}")
@@ -150,7 +117,8 @@ def grid_sample(coord, grid_size=0.02, min_coord=None, mode="train", draws=None,
     lib = load()
     if min_coord is None:
         mins = torch.empty(S, 6, dtype=torch.float32, device=dev)
-        _check(lib.u3d_pointfusion_minmax(N, S, _lib.ptr(offsets), _lib.ptr(coord), _lib.ptr(mins), _stream(dev)), "u3d_pointfusion_minmax")
+        check(lib.u3d_pointfusion_minmax(N, S, _lib.ptr(offsets), _lib.ptr(coord), _lib.ptr(mins), stream_ptr(dev)),
+              "u3d_pointfusion_minmax", named=False)
         stride = 6
     else:
         mins, stride = _min_rows(min_coord, S, dev), 3
@@ -164,8 +132,8 @@ def grid_sample(coord, grid_size=0.02, min_coord=None, mode="train", draws=None,
            "max_count": max_count}
     if return_inverse:
         inverse = torch.empty(N, dtype=torch.int64, device=dev)
-        _check(lib.u3d_pointfusion_inverse(N, N, S, _lib.ptr(offsets), _lib.ptr(voxel_offsets), _lib.ptr(inverse), _lib.ptr(scratch),
-                                           _stream(dev)), "u3d_pointfusion_inverse")
+        check(lib.u3d_pointfusion_inverse(N, N, S, _lib.ptr(offsets), _lib.ptr(voxel_offsets), _lib.ptr(inverse), _lib.ptr(scratch),
+                                          stream_ptr(dev)), "u3d_pointfusion_inverse", named=False)
         out["inverse"] = inverse
     return out
 
@@ -181,8 +149,8 @@ class _PixelGather(torch.autograd.Function):
             raise ValueError(f"feat_2d_all: expected float32, got {f.dtype}")
         M = src.shape[0]
         out = torch.empty(M, C, dtype=torch.float32, device=f.device)
-        _check(load().u3d_pointfusion_gather_forward(M, C, H * W, _lib.ptr(f), _lib.ptr(src), _lib.ptr(out), _stream(f.device)),
-               "u3d_pointfusion_gather_forward")
+        check(load().u3d_pointfusion_gather_forward(M, C, H * W, _lib.ptr(f), _lib.ptr(src), _lib.ptr(out), stream_ptr(f.device)),
+              "u3d_pointfusion_gather_forward", named=False)
         ctx.save_for_backward(src)
         ctx.shape = (V, C, H, W)
         return out
@@ -194,14 +162,14 @@ class _PixelGather(torch.autograd.Function):
         g = grad_out.contiguous().float()
         grad = torch.empty(V, C, H, W, dtype=torch.float32, device=src.device)   # every element written once by the kernel
         pixel_map = torch.empty(V * H * W, dtype=torch.int32, device=src.device)
-        _check(load().u3d_pointfusion_gather_backward(V, C, H * W, src.shape[0], _lib.ptr(g), _lib.ptr(src), _lib.ptr(pixel_map),
-                                                      _lib.ptr(grad), _stream(src.device)), "u3d_pointfusion_gather_backward")
+        check(load().u3d_pointfusion_gather_backward(V, C, H * W, src.shape[0], _lib.ptr(g), _lib.ptr(src), _lib.ptr(pixel_map),
+                                                     _lib.ptr(grad), stream_ptr(src.device)), "u3d_pointfusion_gather_backward", named=False)
         return grad, None
 
 
 def pixel_gather(feat_2d_all, src_pixel):
     """(M,C) rows of the NCHW features at flat (view, row, column) pixel indices src_pixel (int32); differentiable in feat_2d_all."""
-    _on_device(feat_2d_all, src_pixel)
+    on_device("pointfusion", feat_2d_all, src_pixel)
     return _PixelGather.apply(feat_2d_all, src_pixel.to(torch.int32).contiguous())
 
 
@@ -209,7 +177,7 @@ def fuse_pixels(feat_2d_all, unprojected_coord, init_coord, grid_size=0.02, mode
     """The device half of PointFusion.forward: filter (w != 0, inclusive box of init_coord), grid-sample with min = init_coord.min(0),
     gather the picked pixels' features.  Returns None when no pixel survives, else a dict: coord (M,3), grid_coord (M,3) int64,
     feat (M,C), src_pixel (M,) int32 flat (view, row, column) pixel of each voxel's pick, n (points that passed the filters)."""
-    dev = _on_device(feat_2d_all, unprojected_coord, init_coord)
+    dev = on_device("pointfusion", feat_2d_all, unprojected_coord, init_coord)
     uc = unprojected_coord[0].detach().float().contiguous().reshape(-1, 4)
     if uc.data_ptr() % 16:
         uc = uc.clone()
@@ -222,13 +190,13 @@ def fuse_pixels(feat_2d_all, unprojected_coord, init_coord, grid_size=0.02, mode
     init = init_coord.detach().float().contiguous()
     lib = load()
     box = torch.empty(1, 6, dtype=torch.float32, device=dev)    # min xyz, max xyz of init_coord: the box and the grid origin
-    _check(lib.u3d_pointfusion_minmax(init.shape[0], 1, None, _lib.ptr(init), _lib.ptr(box), _stream(dev)), "u3d_pointfusion_minmax")
+    check(lib.u3d_pointfusion_minmax(init.shape[0], 1, None, _lib.ptr(init), _lib.ptr(box), stream_ptr(dev)), "u3d_pointfusion_minmax", named=False)
     scratch = torch.empty(lib.u3d_pointfusion_scratch_bytes(P, 1), dtype=torch.uint8, device=dev)
     meta = torch.empty(4, dtype=torch.int32, device=dev)
     coord = torch.empty(P, 3, dtype=torch.float32, device=dev)
     src_of_point = torch.empty(P, dtype=torch.int32, device=dev)
-    _check(lib.u3d_pointfusion_compact(P, _lib.ptr(uc), _lib.ptr(box), _lib.ptr(coord), _lib.ptr(src_of_point), _lib.ptr(meta),
-                                       _lib.ptr(scratch), _stream(dev)), "u3d_pointfusion_compact")
+    check(lib.u3d_pointfusion_compact(P, _lib.ptr(uc), _lib.ptr(box), _lib.ptr(coord), _lib.ptr(src_of_point), _lib.ptr(meta),
+                                      _lib.ptr(scratch), stream_ptr(dev)), "u3d_pointfusion_compact", named=False)
     voxel_offsets = _voxelize(coord, grid_size, box, 6, 1, None, P, -1, scratch, meta)
     n, M, _, _ = meta.tolist()                      # the call's one device -> host read
     if n == 0:

@@ -13,11 +13,9 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib
+from ._lib import check, on_device, stream_ptr
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_pointops.so")   # (U3D_LIB_DIRNAME: experiment builds, see _lib.py)
-EXPORTS = ("u3d_furthest_point_sampling", "u3d_ball_query", "u3d_group_points", "u3d_group_points_grad",
-           "u3d_gather_points", "u3d_gather_points_grad", "u3d_three_nn", "u3d_three_interpolate", "u3d_three_interpolate_grad",
-           "u3d_pointops_set_contraction", "u3d_pointops_get_contraction", "u3d_group_points_grad_rows", "u3d_three_interpolate_grad_rows")
 CONTRACTIONS = {"fma_llvm": 0, "fma_chain": 1, "none": 2}    # include/unipre3d_pointops.h: U3D_PO_*
 
 
@@ -28,54 +26,32 @@ def set_contraction(mode: str) -> None:
     rc = load().u3d_pointops_set_contraction(CONTRACTIONS[mode])
     if rc != 0:
         raise ValueError(f"unknown contraction mode {mode!r}")
-_po = None
+
+
+_i, _f, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+SIGNATURES = {   # include/unipre3d_pointops.h
+    "u3d_furthest_point_sampling": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_ball_query": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "u3d_group_points": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_group_points_grad": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_gather_points": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_gather_points_grad": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_three_nn": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_three_interpolate": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_three_interpolate_grad": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_pointops_set_contraction": (_i, [_i]),
+    "u3d_pointops_get_contraction": (_i, []),
+    "u3d_group_points_grad_rows": (_i, [_i, _i, _i]),
+    "u3d_three_interpolate_grad_rows": (_i, [_i, _i, _i]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
-    global _po
-    if _po is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing (no fallback): run `make -C unipre3d_amd/csrc`")
-        lib = ctypes.CDLL(LIB_PATH)
-        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        lib.u3d_furthest_point_sampling.argtypes = [i, i, i, vp, vp, vp, vp]
-        lib.u3d_ball_query.argtypes = [i, i, i, f, i, vp, vp, vp, vp]
-        lib.u3d_group_points.argtypes = [i, i, i, i, i, vp, vp, vp, vp]
-        lib.u3d_group_points_grad.argtypes = [i, i, i, i, i, vp, vp, vp, vp]
-        lib.u3d_gather_points.argtypes = [i, i, i, i, vp, vp, vp, vp]
-        lib.u3d_gather_points_grad.argtypes = [i, i, i, i, vp, vp, vp, vp]
-        lib.u3d_three_nn.argtypes = [i, i, i, vp, vp, vp, vp, vp]
-        lib.u3d_three_interpolate.argtypes = [i, i, i, i, vp, vp, vp, vp, vp]
-        lib.u3d_three_interpolate_grad.argtypes = [i, i, i, i, vp, vp, vp, vp, vp]
-        lib.u3d_pointops_set_contraction.argtypes = [i]
-        lib.u3d_pointops_get_contraction.argtypes = []
-        lib.u3d_group_points_grad_rows.argtypes = [i, i, i]
-        lib.u3d_three_interpolate_grad_rows.argtypes = [i, i, i]
-        for n in EXPORTS:
-            getattr(lib, n).restype = ctypes.c_int
-        _po = lib
-    return _po
+    return _lib.open_library("libunipre3d_pointops.so", SIGNATURES)
 
 
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed with code {rc}")
-
-
-def _stream(dev=None):
-    """torch's current stream on the CURRENT device; tensors living on another device are refused (rasterizer._stream_ptr)."""
-    from .rasterizer import _stream_ptr
-    return _stream_ptr(dev)
-
-
-def _need_gpu(*tensors):
-    dev = tensors[0].device
-    for t in tensors:
-        if t.device.type != "cuda":
-            raise RuntimeError("unipre3d_amd.pointops needs tensors on a HIP device; there is no CPU fallback")
-        if t.device != dev:
-            raise RuntimeError(f"unipre3d_amd.pointops: tensors on different devices ({dev} and {t.device})")
-    return dev
+_stream = stream_ptr   # (kept name: callers of the raw C-ABI entry points outside this module take the stream through it)
 
 
 def _f32(t, what):
@@ -100,12 +76,12 @@ class FurthestPointSampling(Function):
     def forward(ctx, xyz: torch.Tensor, npoint: int) -> torch.Tensor:
         """xyz (B,N,3) -> (B,npoint) int32 indices, starting from index 0 (subsample.py:77-100)."""
         assert xyz.is_contiguous()
-        dev = _need_gpu(xyz)
+        dev = on_device("pointops", xyz)
         xyz = _f32(xyz, "xyz")
         B, N, _ = xyz.size()
         out = torch.empty(B, npoint, dtype=torch.int32, device=xyz.device)
         temp = torch.empty(B, N, dtype=torch.float32, device=xyz.device) if N > 8192 else None
-        _check(load().u3d_furthest_point_sampling(B, N, npoint, _lib.ptr(xyz), _lib.ptr(temp), _lib.ptr(out), _stream(dev)), "fps")
+        check(load().u3d_furthest_point_sampling(B, N, npoint, _lib.ptr(xyz), _lib.ptr(temp), _lib.ptr(out), stream_ptr(dev)), "fps", named=False)
         return out
 
     @staticmethod
@@ -121,12 +97,12 @@ class GatherOperation(Function):
     def forward(ctx, features: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         """features (B,C,N), idx (B,npoint) -> (B,C,npoint) (subsample.py:110-131)."""
         assert features.is_contiguous() and idx.is_contiguous()
-        dev = _need_gpu(features, idx)
+        dev = on_device("pointops", features, idx)
         features, idx = _f32(features, "features"), _i32(idx, "idx")
         B, npoint = idx.size()
         _, C, N = features.size()
         out = torch.empty(B, C, npoint, dtype=torch.float32, device=features.device)
-        _check(load().u3d_gather_points(B, C, N, npoint, _lib.ptr(features), _lib.ptr(idx), _lib.ptr(out), _stream(dev)), "gather")
+        check(load().u3d_gather_points(B, C, N, npoint, _lib.ptr(features), _lib.ptr(idx), _lib.ptr(out), stream_ptr(dev)), "gather", named=False)
         ctx.for_backwards = (idx, C, N)
         return out
 
@@ -136,8 +112,8 @@ class GatherOperation(Function):
         B, npoint = idx.size()
         grad = torch.zeros(B, C, N, dtype=torch.float32, device=grad_out.device)
         g = _f32(grad_out, "grad_out").contiguous()
-        _check(load().u3d_gather_points_grad(B, C, N, npoint, _lib.ptr(g), _lib.ptr(idx), _lib.ptr(grad), _stream(_need_gpu(g, idx))),
-               "gather grad")
+        check(load().u3d_gather_points_grad(B, C, N, npoint, _lib.ptr(g), _lib.ptr(idx), _lib.ptr(grad), stream_ptr(on_device("pointops", g, idx))),
+              "gather grad", named=False)
         return grad, None
 
 
@@ -155,13 +131,13 @@ class GroupingOperation(Function):
     def forward(ctx, features: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         """features (B,C,N), idx (B,npoint,nsample) -> (B,C,npoint,nsample) (group.py:76-99)."""
         assert features.is_contiguous() and idx.is_contiguous()
-        dev = _need_gpu(features, idx)
+        dev = on_device("pointops", features, idx)
         features, idx = _f32(features, "features"), _i32(idx, "idx")
         B, npoint, nsample = idx.size()
         _, C, N = features.size()
         out = torch.empty(B, C, npoint, nsample, dtype=torch.float32, device=features.device)
-        _check(load().u3d_group_points(B, C, N, npoint, nsample, _lib.ptr(features), _lib.ptr(idx), _lib.ptr(out), _stream(dev)),
-               "group")
+        check(load().u3d_group_points(B, C, N, npoint, nsample, _lib.ptr(features), _lib.ptr(idx), _lib.ptr(out), stream_ptr(dev)),
+              "group", named=False)
         ctx.for_backwards = (idx, N)
         return out
 
@@ -171,8 +147,8 @@ class GroupingOperation(Function):
         B, C, npoint, nsample = grad_out.size()
         grad = torch.zeros(B, C, N, dtype=torch.float32, device=grad_out.device)
         g = _f32(grad_out, "grad_out").contiguous()
-        _check(load().u3d_group_points_grad(B, C, N, npoint, nsample, _lib.ptr(g), _lib.ptr(idx), _lib.ptr(grad),
-                                            _stream(_need_gpu(g, idx))), "group grad")
+        check(load().u3d_group_points_grad(B, C, N, npoint, nsample, _lib.ptr(g), _lib.ptr(idx), _lib.ptr(grad),
+                                           stream_ptr(on_device("pointops", g, idx))), "group grad", named=False)
         return grad, None
 
 
@@ -184,13 +160,13 @@ class BallQuery(Function):
     def forward(ctx, radius: float, nsample: int, xyz: torch.Tensor, new_xyz: torch.Tensor) -> torch.Tensor:
         """xyz (B,N,3) support, new_xyz (B,npoint,3) centres -> (B,npoint,nsample) int32 (group.py:175-196)."""
         assert new_xyz.is_contiguous() and xyz.is_contiguous()
-        dev = _need_gpu(xyz, new_xyz)
+        dev = on_device("pointops", xyz, new_xyz)
         xyz, new_xyz = _f32(xyz, "xyz"), _f32(new_xyz, "new_xyz")
         B, N, _ = xyz.size()
         npoint = new_xyz.size(1)
         idx = torch.empty(B, npoint, nsample, dtype=torch.int32, device=xyz.device)
-        _check(load().u3d_ball_query(B, N, npoint, float(radius), nsample, _lib.ptr(new_xyz), _lib.ptr(xyz), _lib.ptr(idx), _stream(dev)),
-               "ball query")
+        check(load().u3d_ball_query(B, N, npoint, float(radius), nsample, _lib.ptr(new_xyz), _lib.ptr(xyz), _lib.ptr(idx), stream_ptr(dev)),
+              "ball query", named=False)
         return idx
 
     @staticmethod
@@ -207,13 +183,14 @@ class ThreeNN(Function):
         """unknown (B,N,3), known (B,M,3) -> (dist (B,N,3) L2 distances to the three nearest known points, idx (B,N,3) int32)
         (upsampling.py:11-35; the kernel returns squared distances, the wrapper takes the root like the reference)."""
         assert unknown.is_contiguous() and known.is_contiguous()
-        dev = _need_gpu(unknown, known)
+        dev = on_device("pointops", unknown, known)
         unknown, known = _f32(unknown, "unknown"), _f32(known, "known")
         B, N, _ = unknown.size()
         m = known.size(1)
         dist2 = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
         idx = torch.empty(B, N, 3, dtype=torch.int32, device=dev)
-        _check(load().u3d_three_nn(B, N, m, _lib.ptr(unknown), _lib.ptr(known), _lib.ptr(dist2), _lib.ptr(idx), _stream(dev)), "three_nn")
+        check(load().u3d_three_nn(B, N, m, _lib.ptr(unknown), _lib.ptr(known), _lib.ptr(dist2), _lib.ptr(idx), stream_ptr(dev)),
+              "three_nn", named=False)
         return torch.sqrt(dist2), idx
 
     @staticmethod
@@ -230,14 +207,14 @@ class ThreeInterpolate(Function):
         """features (B,C,M), idx (B,n,3), weight (B,n,3) -> (B,C,n) (upsampling.py:43-67; inputs are cast to fp32 like the
         reference's custom_fwd(cast_inputs=torch.float32))."""
         assert features.is_contiguous() and idx.is_contiguous() and weight.is_contiguous()
-        dev = _need_gpu(features, idx, weight)
+        dev = on_device("pointops", features, idx, weight)
         features, idx, weight = _f32(features, "features"), _i32(idx, "idx"), _f32(weight, "weight")
         B, c, m = features.size()
         n = idx.size(1)
         ctx.three_interpolate_for_backward = (idx, weight, m)
         out = torch.empty(B, c, n, dtype=torch.float32, device=dev)
-        _check(load().u3d_three_interpolate(B, c, m, n, _lib.ptr(features), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(out), _stream(dev)),
-               "three_interpolate")
+        check(load().u3d_three_interpolate(B, c, m, n, _lib.ptr(features), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(out), stream_ptr(dev)),
+              "three_interpolate", named=False)
         return out
 
     @staticmethod
@@ -246,8 +223,8 @@ class ThreeInterpolate(Function):
         B, c, n = grad_out.size()
         grad_features = torch.zeros(B, c, m, dtype=torch.float32, device=grad_out.device)
         g = _f32(grad_out, "grad_out").contiguous()
-        _check(load().u3d_three_interpolate_grad(B, c, n, m, _lib.ptr(g), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(grad_features),
-                                                 _stream(_need_gpu(g, idx, weight))), "three_interpolate grad")
+        check(load().u3d_three_interpolate_grad(B, c, n, m, _lib.ptr(g), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(grad_features),
+                                                stream_ptr(on_device("pointops", g, idx, weight))), "three_interpolate grad", named=False)
         return grad_features, None, None
 
 

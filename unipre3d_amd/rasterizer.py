@@ -122,21 +122,7 @@ def ragged_layout(sizes, device):
     return hit
 
 
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream_ptr(dev=None):
-    """torch's CURRENT stream on the current device as a hipStream_t (the raw-handle query costs ~0.3 us, the Stream object
-    route ~10 us per call).  The kernels are launched on the calling thread's current HIP device, so tensors on another
-    device are refused instead of being launched against the wrong queue."""
-    cur = torch.cuda.current_device()
-    if dev is not None and dev.index is not None and dev.index != cur:
-        raise RuntimeError(f"tensors live on cuda:{dev.index} but the current device is cuda:{cur}; "
-                           f"call under torch.cuda.device({dev.index}) (one process per GPU sets it once)")
-    if _raw_stream is not None:
-        return ctypes.c_void_p(_raw_stream(cur))
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
+_stream_ptr = _lib.stream_ptr   # (the name fused.py, dp.py and the benchmark reach it by)
 
 _BINDING_PATH = os.path.join(_lib.LIB_DIR, "_u3d_torch.so")
 _binding = None

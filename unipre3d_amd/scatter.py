@@ -11,7 +11,8 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .attention import _check, _on_device, _stream, load
+from ._lib import check, on_device, stream_ptr
+from .attention import load
 
 REDUCE = {"sum": 0, "add": 0, "mean": 1, "max": 2, "min": 3}
 EXPORTS = ("u3d_segment_csr_fwd", "u3d_segment_csr_bwd")
@@ -24,8 +25,8 @@ class _SegmentCSR(torch.autograd.Function):
         M = indptr.numel() - 1
         out = torch.empty(M, C, dtype=torch.float32, device=src.device)
         arg = torch.empty(M, C, dtype=torch.int64, device=src.device) if reduce >= 2 else None
-        _check(load().u3d_segment_csr_fwd(_lib.ptr(src), _lib.ptr(indptr), _lib.ptr(out), _lib.ptr(arg), N, M, C, reduce,
-                                          _stream(src.device)), "u3d_segment_csr_fwd")
+        check(load().u3d_segment_csr_fwd(_lib.ptr(src), _lib.ptr(indptr), _lib.ptr(out), _lib.ptr(arg), N, M, C, reduce,
+                                         stream_ptr(src.device)), "u3d_segment_csr_fwd", named=False)
         ctx.save_for_backward(indptr, arg)
         ctx.args = (N, M, C, reduce)
         ctx.mark_non_differentiable(indptr)
@@ -37,8 +38,8 @@ class _SegmentCSR(torch.autograd.Function):
         N, M, C, reduce = ctx.args
         dout = dout.to(torch.float32).contiguous()
         dsrc = torch.empty(N, C, dtype=torch.float32, device=dout.device)
-        _check(load().u3d_segment_csr_bwd(_lib.ptr(dout), _lib.ptr(indptr), _lib.ptr(arg), _lib.ptr(dsrc), N, M, C, reduce,
-                                          _stream(dout.device)), "u3d_segment_csr_bwd")
+        check(load().u3d_segment_csr_bwd(_lib.ptr(dout), _lib.ptr(indptr), _lib.ptr(arg), _lib.ptr(dsrc), N, M, C, reduce,
+                                         stream_ptr(dout.device)), "u3d_segment_csr_bwd", named=False)
         return dsrc, None, None
 
 
@@ -49,7 +50,7 @@ def segment_csr(src, indptr, out=None, reduce="sum"):
     if reduce not in REDUCE:
         raise ValueError(f"reduce={reduce!r}: expected one of sum, mean, max, min")
     load()
-    _on_device("scatter", src, indptr)
+    on_device("scatter", src, indptr)
     if src.dim() != 2 or indptr.dim() != 1:
         raise NotImplementedError(f"segment_csr: src (N, C) with indptr (M+1,) only, got {tuple(src.shape)} and {tuple(indptr.shape)}")
     if src.dtype != torch.float32:

@@ -21,40 +21,30 @@ import os
 import torch
 
 from . import _lib
-from .attention import _check, _on_device, _stream
+from ._lib import check, on_device, stream_ptr
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_serialization.so")
-EXPORTS = ("u3d_ser_abi_version", "u3d_ser_scratch_bytes", "u3d_ser_encode", "u3d_ser_sort", "u3d_ser_serialize",
-           "u3d_ser_patch_padding", "u3d_ser_pool_count", "u3d_ser_pool_emit")
 ABI_VERSION = 1
 ORDERS = {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
 MAX_ORDERS = 4
 MAX_ROWS = 1 << 30
-_se = None
+
+_i, _ll, _vp = ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p
+SIGNATURES = {   # include/unipre3d_serialization.h
+    "u3d_ser_abi_version": (_i, []),
+    "u3d_ser_scratch_bytes": (ctypes.c_size_t, [_i, _i]),
+    "u3d_ser_encode": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "u3d_ser_sort": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_ser_serialize": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_ser_patch_padding": (_i, [_i, _i, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_ser_pool_count": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_ser_pool_emit": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
-    global _se
-    if _se is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing (no fallback): run `make -C unipre3d_amd/csrc`")
-        lib = ctypes.CDLL(LIB_PATH)
-        vp, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-        lib.u3d_ser_abi_version.argtypes = []
-        lib.u3d_ser_scratch_bytes.argtypes = [i, i]
-        lib.u3d_ser_encode.argtypes = [i, vp, i, vp, i, i, i, i, vp, vp]
-        lib.u3d_ser_sort.argtypes = [i, i, i, vp, vp, vp, vp, vp]
-        lib.u3d_ser_serialize.argtypes = [i, vp, i, vp, i, i, i, i, i, vp, vp, vp, vp, vp]
-        lib.u3d_ser_patch_padding.argtypes = [i, i, ll, ll, ll, vp, vp, vp, vp, vp]
-        lib.u3d_ser_pool_count.argtypes = [i, i, i, i, vp, vp, vp, vp]
-        lib.u3d_ser_pool_emit.argtypes = [i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        for n in EXPORTS:
-            getattr(lib, n).restype = ctypes.c_int
-        lib.u3d_ser_scratch_bytes.restype = ctypes.c_size_t
-        if lib.u3d_ser_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH}: ABI {lib.u3d_ser_abi_version()}, this module binds ABI {ABI_VERSION}: rebuild")
-        _se = lib
-    return _se
+    return _lib.open_library("libunipre3d_serialization.so", SIGNATURES, ("u3d_ser_abi_version", ABI_VERSION))
 
 
 def _order_bits(orders):
@@ -74,7 +64,7 @@ def _order_bits(orders):
 def _check_points(grid_coord, batch, depth, batch_size):
     """Validates the inputs of encode / serialize; returns (device, key width in bits)."""
     ts = (grid_coord,) if batch is None else (grid_coord, batch)
-    dev = _on_device("serialization", *ts)
+    dev = on_device("serialization", *ts)
     if grid_coord.dim() != 2 or grid_coord.shape[1] != 3:
         raise ValueError(f"grid_coord: expected (N, 3), got {tuple(grid_coord.shape)}")
     N = grid_coord.shape[0]
@@ -108,7 +98,7 @@ def _check_points(grid_coord, batch, depth, batch_size):
 
 
 def _check_code(code):
-    dev = _on_device("serialization", code)
+    dev = on_device("serialization", code)
     if code.dim() != 2 or code.dtype != torch.int64:
         raise ValueError(f"code: expected a (K, N) int64 tensor, got {tuple(code.shape)} {code.dtype}")
     K, N = code.shape
@@ -138,9 +128,9 @@ def encode(grid_coord, batch=None, depth=16, order="z"):
     dev, _ = _check_points(grid_coord, batch, depth, None)
     N = grid_coord.shape[0]
     code = torch.empty(K, N, dtype=torch.int64, device=dev)
-    _check(lib.u3d_ser_encode(N, _lib.ptr(grid_coord), int(grid_coord.dtype == torch.int64), _lib.ptr(batch),
-                              int(batch is not None and batch.dtype == torch.int64), depth, K, bits, _lib.ptr(code), _stream(dev)),
-           "u3d_ser_encode")
+    check(lib.u3d_ser_encode(N, _lib.ptr(grid_coord), int(grid_coord.dtype == torch.int64), _lib.ptr(batch),
+                             int(batch is not None and batch.dtype == torch.int64), depth, K, bits, _lib.ptr(code), stream_ptr(dev)),
+          "u3d_ser_encode", named=False)
     return code[0] if isinstance(order, str) else code
 
 
@@ -153,8 +143,8 @@ def sort_codes(code, key_bits=63):
         raise ValueError(f"key_bits={key_bits}: 1 .. 63")
     order, inverse = torch.empty_like(code), torch.empty_like(code)
     scratch = _scratch(lib, K, N, dev)
-    _check(lib.u3d_ser_sort(K, N, int(key_bits), _lib.ptr(code), _lib.ptr(order), _lib.ptr(inverse), _lib.ptr(scratch), _stream(dev)),
-           "u3d_ser_sort")
+    check(lib.u3d_ser_sort(K, N, int(key_bits), _lib.ptr(code), _lib.ptr(order), _lib.ptr(inverse), _lib.ptr(scratch), stream_ptr(dev)),
+          "u3d_ser_sort", named=False)
     return order, inverse
 
 
@@ -170,9 +160,9 @@ def serialize(grid_coord, batch, depth, orders, batch_size=None, shuffle_orders=
     code = torch.empty(K, N, dtype=torch.int64, device=dev)
     order, inverse = torch.empty_like(code), torch.empty_like(code)
     scratch = _scratch(lib, K, N, dev)
-    _check(lib.u3d_ser_serialize(N, _lib.ptr(grid_coord), int(grid_coord.dtype == torch.int64), _lib.ptr(batch),
-                                 int(batch is not None and batch.dtype == torch.int64), depth, K, bits, key_bits, _lib.ptr(code),
-                                 _lib.ptr(order), _lib.ptr(inverse), _lib.ptr(scratch), _stream(dev)), "u3d_ser_serialize")
+    check(lib.u3d_ser_serialize(N, _lib.ptr(grid_coord), int(grid_coord.dtype == torch.int64), _lib.ptr(batch),
+                                int(batch is not None and batch.dtype == torch.int64), depth, K, bits, key_bits, _lib.ptr(code),
+                                _lib.ptr(order), _lib.ptr(inverse), _lib.ptr(scratch), stream_ptr(dev)), "u3d_ser_serialize", named=False)
     if shuffle_orders:
         perm = torch.randperm(K).to(dev)
         code, order, inverse = code[perm], order[perm], inverse[perm]
@@ -215,8 +205,8 @@ def patch_padding(offset, patch_size, device=None):
     pad = torch.empty(T_pad, dtype=torch.int64, device=dev)
     unpad = torch.empty(T, dtype=torch.int64, device=dev)
     cu = torch.empty(S + 1, dtype=torch.int32, device=dev)
-    _check(lib.u3d_ser_patch_padding(B, P, T, T_pad, S, _lib.ptr(meta), _lib.ptr(pad), _lib.ptr(unpad), _lib.ptr(cu), _stream(dev)),
-           "u3d_ser_patch_padding")
+    check(lib.u3d_ser_patch_padding(B, P, T, T_pad, S, _lib.ptr(meta), _lib.ptr(pad), _lib.ptr(unpad), _lib.ptr(cu), stream_ptr(dev)),
+          "u3d_ser_patch_padding", named=False)
     return pad, unpad, cu
 
 
@@ -236,15 +226,15 @@ def pool_clusters(code, pooling_depth, depth=None, batch_size=None):
         if not 1 <= int(depth) <= 16 or pd > int(depth) or int(batch_size) < 1 or 3 * int(depth) + int(batch_size).bit_length() > 63:
             raise ValueError(f"depth={depth}, batch_size={batch_size}, pooling_depth={pd}: not a serialization's")
         key_bits = max(3 * (int(depth) - pd) + (int(batch_size) - 1).bit_length(), 1)
-    st = _stream(dev)
+    st = stream_ptr(dev)
     scratch = _scratch(lib, K, N, dev)
     meta = torch.empty(4, dtype=torch.int32, device=dev)
-    _check(lib.u3d_ser_pool_count(K, N, 3 * pd, key_bits, _lib.ptr(code), _lib.ptr(meta), _lib.ptr(scratch), st), "u3d_ser_pool_count")
+    check(lib.u3d_ser_pool_count(K, N, 3 * pd, key_bits, _lib.ptr(code), _lib.ptr(meta), _lib.ptr(scratch), st), "u3d_ser_pool_count", named=False)
     M = int(meta[0].item())                    # the one device -> host read: the cluster count
     new = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
     cluster, indices, idx_ptr, head = new(N), new(N), new(M + 1), new(M)
     pcode, porder, pinverse = new(K, M), new(K, M), new(K, M)
-    _check(lib.u3d_ser_pool_emit(K, N, M, 3 * pd, key_bits, _lib.ptr(code), _lib.ptr(cluster), _lib.ptr(indices), _lib.ptr(idx_ptr),
-                                 _lib.ptr(head), _lib.ptr(pcode), _lib.ptr(porder), _lib.ptr(pinverse), _lib.ptr(scratch), st),
-           "u3d_ser_pool_emit")
+    check(lib.u3d_ser_pool_emit(K, N, M, 3 * pd, key_bits, _lib.ptr(code), _lib.ptr(cluster), _lib.ptr(indices), _lib.ptr(idx_ptr),
+                                _lib.ptr(head), _lib.ptr(pcode), _lib.ptr(porder), _lib.ptr(pinverse), _lib.ptr(scratch), st),
+          "u3d_ser_pool_emit", named=False)
     return cluster, indices, idx_ptr, head, pcode, porder, pinverse

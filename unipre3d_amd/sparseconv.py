@@ -32,64 +32,30 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import check, on_device, stream_ptr
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_sparseconv.so")
-EXPORTS = ("u3d_spconv_abi_version", "u3d_spconv_scratch_bytes", "u3d_spconv_subm_map", "u3d_spconv_down_map", "u3d_spconv_down_emit",
-           "u3d_spconv_gemm", "u3d_spconv_dupsum", "u3d_spconv_wgrad_partial_floats", "u3d_spconv_wgrad",
-           "u3d_spconv_colsum_partial_floats", "u3d_spconv_colsum")
 ABI_VERSION = 1
-_sc = None
+
+_i, _vp, _size = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
+SIGNATURES = {   # include/unipre3d_sparseconv.h
+    "u3d_spconv_abi_version": (_i, []),
+    "u3d_spconv_scratch_bytes": (_size, [_i]),
+    "u3d_spconv_subm_map": (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_spconv_down_map": (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "u3d_spconv_down_emit": (_i, [_i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_spconv_gemm": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_spconv_dupsum": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_spconv_wgrad_partial_floats": (_size, [_i, _i, _i, _i]),
+    "u3d_spconv_wgrad": (_i, [_i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_spconv_colsum_partial_floats": (_size, [_i, _i]),
+    "u3d_spconv_colsum": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def load() -> ctypes.CDLL:
-    global _sc
-    if _sc is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing (no fallback): run `make -C unipre3d_amd/csrc`")
-        lib = ctypes.CDLL(LIB_PATH)
-        vp, i = ctypes.c_void_p, ctypes.c_int
-        lib.u3d_spconv_abi_version.argtypes = []
-        lib.u3d_spconv_scratch_bytes.argtypes = [i]
-        lib.u3d_spconv_subm_map.argtypes = [i, vp, i, i, i, i, i, vp, vp, vp, vp, vp]
-        lib.u3d_spconv_down_map.argtypes = [i, vp, i, i, i, i, i, vp, vp, vp]
-        lib.u3d_spconv_down_emit.argtypes = [i, i, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.u3d_spconv_gemm.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.u3d_spconv_dupsum.argtypes = [i, i, vp, vp, vp, vp, vp]
-        lib.u3d_spconv_wgrad_partial_floats.argtypes = [i, i, i, i]
-        lib.u3d_spconv_wgrad.argtypes = [i, i, i, i, vp, i, vp, vp, vp, vp, vp]
-        lib.u3d_spconv_colsum_partial_floats.argtypes = [i, i]
-        lib.u3d_spconv_colsum.argtypes = [i, i, vp, vp, vp, vp]
-        for n in EXPORTS:
-            getattr(lib, n).restype = ctypes.c_int
-        for n in ("u3d_spconv_scratch_bytes", "u3d_spconv_wgrad_partial_floats", "u3d_spconv_colsum_partial_floats"):
-            getattr(lib, n).restype = ctypes.c_size_t
-        if lib.u3d_spconv_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH}: ABI {lib.u3d_spconv_abi_version()}, this module binds ABI {ABI_VERSION}: rebuild")
-        _sc = lib
-    return _sc
-
-
-def _check(rc, name):
-    if rc != 0:
-        raise RuntimeError(f"{name} failed with code {rc}")
-
-
-def _stream(dev):
-    from .rasterizer import _stream_ptr
-    return _stream_ptr(dev)
-
-
-def _device(*ts):
-    dev = None
-    for t in ts:
-        if t is None:
-            continue
-        if t.device.type != "cuda":
-            raise RuntimeError("unipre3d_amd.sparseconv needs tensors on a HIP device; there is no CPU fallback")
-        if dev is not None and t.device != dev:
-            raise RuntimeError(f"unipre3d_amd.sparseconv: tensors on different devices ({dev}, {t.device})")
-        dev = t.device
-    return dev
+    return _lib.open_library("libunipre3d_sparseconv.so", SIGNATURES, ("u3d_spconv_abi_version", ABI_VERSION))
 
 
 def _indices(indices):
@@ -129,7 +95,7 @@ class DownMap:
 
 
 def subm_map(indices, spatial_shape, batch_size, k) -> SubMMap:
-    dev = _device(indices)
+    dev = on_device("sparseconv", indices)
     idx = _indices(indices)
     D = _shape3(spatial_shape)
     N, K = idx.shape[0], k ** 3
@@ -138,13 +104,13 @@ def subm_map(indices, spatial_shape, batch_size, k) -> SubMMap:
     first = torch.empty(N, dtype=torch.int32, device=dev)
     nxt = torch.empty(N, dtype=torch.int32, device=dev)
     scratch = torch.empty(max(lib.u3d_spconv_scratch_bytes(N), 1), dtype=torch.uint8, device=dev)
-    _check(lib.u3d_spconv_subm_map(N, _lib.ptr(idx), int(batch_size), D[0], D[1], D[2], k, _lib.ptr(table), _lib.ptr(first),
-                                   _lib.ptr(nxt), _lib.ptr(scratch), _stream(dev)), "u3d_spconv_subm_map")
+    check(lib.u3d_spconv_subm_map(N, _lib.ptr(idx), int(batch_size), D[0], D[1], D[2], k, _lib.ptr(table), _lib.ptr(first),
+                                  _lib.ptr(nxt), _lib.ptr(scratch), stream_ptr(dev)), "u3d_spconv_subm_map", named=False)
     return SubMMap(k, table, first, nxt)
 
 
 def down_map(indices, spatial_shape, batch_size, s) -> DownMap:
-    dev = _device(indices)
+    dev = on_device("sparseconv", indices)
     idx = _indices(indices)
     D = _shape3(spatial_shape)
     if min(D) < s:
@@ -153,9 +119,9 @@ def down_map(indices, spatial_shape, batch_size, s) -> DownMap:
     lib = load()
     scratch = torch.empty(max(lib.u3d_spconv_scratch_bytes(N), 1), dtype=torch.uint8, device=dev)
     meta = torch.empty(4, dtype=torch.int32, device=dev)
-    st = _stream(dev)
-    _check(lib.u3d_spconv_down_map(N, _lib.ptr(idx), int(batch_size), D[0], D[1], D[2], s, _lib.ptr(meta), _lib.ptr(scratch), st),
-           "u3d_spconv_down_map")
+    st = stream_ptr(dev)
+    check(lib.u3d_spconv_down_map(N, _lib.ptr(idx), int(batch_size), D[0], D[1], D[2], s, _lib.ptr(meta), _lib.ptr(scratch), st),
+          "u3d_spconv_down_map", named=False)
     M = int(meta[0].item())                    # the map's one device -> host read: the output count
     out_indices = torch.empty(M, 4, dtype=torch.int32, device=dev)
     table = torch.empty(M, K, dtype=torch.int32, device=dev)
@@ -163,9 +129,9 @@ def down_map(indices, spatial_shape, batch_size, s) -> DownMap:
     nxt = torch.empty(N, dtype=torch.int32, device=dev)
     list_row = torch.empty(N, dtype=torch.int32, device=dev)
     list_src = torch.empty(N, dtype=torch.int32, device=dev)
-    _check(lib.u3d_spconv_down_emit(N, M, _lib.ptr(idx), int(batch_size), D[0], D[1], D[2], s, _lib.ptr(out_indices), _lib.ptr(table),
-                                    _lib.ptr(first), _lib.ptr(nxt), _lib.ptr(list_row), _lib.ptr(list_src), _lib.ptr(scratch), st),
-           "u3d_spconv_down_emit")
+    check(lib.u3d_spconv_down_emit(N, M, _lib.ptr(idx), int(batch_size), D[0], D[1], D[2], s, _lib.ptr(out_indices), _lib.ptr(table),
+                                   _lib.ptr(first), _lib.ptr(nxt), _lib.ptr(list_row), _lib.ptr(list_src), _lib.ptr(scratch), st),
+          "u3d_spconv_down_emit", named=False)
     out_shape = [(d - s) // s + 1 for d in D]
     return DownMap(s, idx, D, out_indices, out_shape, table, first, nxt, list_row, list_src)
 
@@ -177,15 +143,15 @@ def _gemm(R, K, A, W, bias, table, list_row=None, mask=None, out_rows=None):
     if A.shape[0] == 0:   # a strided conv that dropped every row: no entry has a source, the rows are bias (or 0); never read
         A = A.new_zeros(1, Cin)
     Y = torch.empty(R if out_rows is None else out_rows, Cout, dtype=torch.float32, device=A.device)
-    _check(load().u3d_spconv_gemm(R, K, Cin, Cout, _lib.ptr(table), _lib.ptr(list_row), _lib.ptr(A), _lib.ptr(W), _lib.ptr(bias),
-                                  _lib.ptr(mask), _lib.ptr(Y), _stream(A.device)), "u3d_spconv_gemm")
+    check(load().u3d_spconv_gemm(R, K, Cin, Cout, _lib.ptr(table), _lib.ptr(list_row), _lib.ptr(A), _lib.ptr(W), _lib.ptr(bias),
+                                 _lib.ptr(mask), _lib.ptr(Y), stream_ptr(A.device)), "u3d_spconv_gemm", named=False)
     return Y
 
 
 def _dupsum(X, first, nxt):
     out = torch.empty_like(X)
-    _check(load().u3d_spconv_dupsum(X.shape[0], X.shape[1], _lib.ptr(first), _lib.ptr(nxt), _lib.ptr(X), _lib.ptr(out),
-                                    _stream(X.device)), "u3d_spconv_dupsum")
+    check(load().u3d_spconv_dupsum(X.shape[0], X.shape[1], _lib.ptr(first), _lib.ptr(nxt), _lib.ptr(X), _lib.ptr(out),
+                                   stream_ptr(X.device)), "u3d_spconv_dupsum", named=False)
     return out
 
 
@@ -195,8 +161,8 @@ def _wgrad(R, K, A, G, table, gather_g):
     lib = load()
     part = torch.empty(max(lib.u3d_spconv_wgrad_partial_floats(R, K, Cin, Cout), 1), dtype=torch.float32, device=A.device)
     dW = torch.empty(K, Cin, Cout, dtype=torch.float32, device=A.device)
-    _check(lib.u3d_spconv_wgrad(R, K, Cin, Cout, _lib.ptr(table), int(gather_g), _lib.ptr(A), _lib.ptr(G), _lib.ptr(part), _lib.ptr(dW),
-                                _stream(A.device)), "u3d_spconv_wgrad")
+    check(lib.u3d_spconv_wgrad(R, K, Cin, Cout, _lib.ptr(table), int(gather_g), _lib.ptr(A), _lib.ptr(G), _lib.ptr(part), _lib.ptr(dW),
+                               stream_ptr(A.device)), "u3d_spconv_wgrad", named=False)
     return dW
 
 
@@ -205,7 +171,7 @@ def _colsum(G):
     lib = load()
     part = torch.empty(max(lib.u3d_spconv_colsum_partial_floats(R, C), 1), dtype=torch.float32, device=G.device)
     db = torch.empty(C, dtype=torch.float32, device=G.device)
-    _check(lib.u3d_spconv_colsum(R, C, _lib.ptr(G), _lib.ptr(part), _lib.ptr(db), _stream(G.device)), "u3d_spconv_colsum")
+    check(lib.u3d_spconv_colsum(R, C, _lib.ptr(G), _lib.ptr(part), _lib.ptr(db), stream_ptr(G.device)), "u3d_spconv_colsum", named=False)
     return db
 
 
@@ -425,7 +391,7 @@ class _SparseConvNd(SparseModule):
             raise TypeError(f"{type(self).__name__} takes a SparseConvTensor, got {type(x).__name__}")
         if x.features.shape[1] != self.in_channels:
             raise ValueError(f"{type(self).__name__}: {x.features.shape[1]} input channels, expected {self.in_channels}")
-        _device(x.features, x.indices)
+        on_device("sparseconv", x.features, x.indices)
 
 
 class SubMConv3d(_SparseConvNd):
