@@ -72,8 +72,8 @@ int u3d_three_interpolate_grad(int b, int c, int n, int m, const float* grad_out
 
 /*
  * Which kernel the two scatter-add gradients launch for a shape: the channel rows one workgroup accumulates in LDS (1, 2, 4, 8 or 16),
- * or 0 for the global-atomic kernel (a row of n resp. m floats does not fit).  The launch and the query share one helper, the
- * U3D_GG_CB / U3D_IG_CB experiment switches included; host arithmetic only, no device is touched (tests ask it without a GPU).
+ * or 0 for the global-atomic kernel (a row of n resp. m floats does not fit).  The launch and the query share one helper;
+ * host arithmetic only, no device is touched (tests ask it without a GPU).
  * u3d_gather_points_grad is u3d_group_points_grad with nsample = 1 and selects alike.
  */
 int u3d_group_points_grad_rows(int b, int c, int n);

@@ -176,6 +176,25 @@ def test_product_never_imports_oracle():
     assert "oracle" not in src
 
 
+def test_product_libraries_carry_no_switches(lib):
+    """No environment switch in the product build: a library of the default directory neither names a `U3D_` variable (exports are
+    lower-case `u3d_`, the error table holds no such string) nor imports `getenv`.  Experiment and diagnostic builds live in other
+    directories (`make LIBDIR=../lib_x EXTRA=-D...`)."""
+    import glob
+    import shutil
+    import subprocess
+    libs = sorted(glob.glob(os.path.join(os.path.dirname(_lib.__file__), "lib", "libunipre3d_*.so")))
+    assert len(libs) >= len(LIBRARIES), libs
+    for path in libs:
+        assert b"U3D_" not in open(path, "rb").read(), path
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("binutils' nm is not installed: the libraries' undefined symbols were not inspected (their bytes were)")
+    for path in libs:
+        undefined = subprocess.run([nm, "-D", "--undefined-only", path], capture_output=True, text=True, check=True).stdout
+        assert "getenv" not in {line.split()[-1].split("@")[0] for line in undefined.splitlines() if line.strip()}, path
+
+
 def _xcd_chunk_in_view(j, view, T):
     """Host restatement of `u3d_xcd_chunk_in_view` (unipre3d_amd/csrc/u3d_common.h): the tile kernels run a (T, views) grid; the
     workgroup with x index j of view `view` has linear id view*T + j and sits on XCD (view*T + j) % 8; within a view the blocks of

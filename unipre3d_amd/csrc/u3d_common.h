@@ -20,12 +20,7 @@ static_assert(U3D_LDS_SORT_MAX == U3D_SPARSE_BWD_MIN_P, "the public header's spa
 // latency-bound), large tiles keep the per-block offset scan short
 // radix workgroup shapes (threads x keys per thread and pass), measured sweep on C4 (40 k keys/view) and C5 (200 k):
 // 1024 x 2 up to 64 k keys, 1024 x 4 beyond (256 x 4 / 256 x 8: 70 / 122 us; 1024 x 2 / 1024 x 4: 66 / 107 us)
-#ifndef U3D_RADIX_NT_SMALL
-#define U3D_RADIX_NT_SMALL 1024
-#define U3D_RADIX_IT_SMALL 2
-#define U3D_RADIX_NT_LARGE 1024
-#define U3D_RADIX_IT_LARGE 4
-#endif
+constexpr int U3D_RADIX_NT_SMALL = 1024, U3D_RADIX_IT_SMALL = 2, U3D_RADIX_NT_LARGE = 1024, U3D_RADIX_IT_LARGE = 4;
 static inline int u3d_radix_tile(int P) { return P <= 65536 ? U3D_RADIX_NT_SMALL * U3D_RADIX_IT_SMALL : U3D_RADIX_NT_LARGE * U3D_RADIX_IT_LARGE; }
 #define U3D_MSD_BINS_MAX 2048          /* depth buckets of the large-P sort's first partition (u3d_sort.hip): 512, 1024 beyond 64 k per view, 2048 beyond 256 k */
 static inline int u3d_msd_bins(int P) { return P <= 65536 ? 512 : (P <= 262144 ? 1024 : 2048); }
@@ -306,14 +301,9 @@ __device__ __forceinline__ uint32_t u3d_xcd_remap(uint32_t bid, uint32_t nblocks
 // bottom rows walk 5 % more entries than the centre, and the two XCDs that own them finished 7.5 us after the first (152 .. 159 us).  When the
 // chunks are equal (T % 8 == 0) the chunk an XCD takes rotates with `rot` (the tile kernels pass the view at object level, P <= 256: C2 render_fb
 // scope 174.1 -> 171.2 us in five alternating pairs; 0 at scene level, where the rotation measured +0.2 ... +1.7 us on C3 / C4 / C5), so every XCD
-// sees every region: U3D_XCD_ROTATE (0 = round 5's map).
-#ifndef U3D_XCD_ROTATE
-#define U3D_XCD_ROTATE 1
-#endif
+// sees every region.
 __device__ __forceinline__ uint32_t u3d_xcd_chunk_in_view(uint32_t j, uint32_t view, uint32_t T, uint32_t rot = 0u) {   // tile (within the view) of block j
-#if U3D_XCD_ROTATE
   if ((T & 7u) == 0u) return (((j + rot) & 7u) * (T >> 3)) + (j >> 3);   // block j sits on XCD j % 8 (view * T is a multiple of 8)
-#endif
   const uint32_t r = (view * T) & 7u, m = r + j, x = m & 7u;
   auto below = [](uint32_t n, uint32_t c) { return (n >> 3) * c + min(n & 7u, c); };   // #{i < n : i % 8 < c}
   const uint32_t k = ((m + 7u - x) >> 3) - ((r + 7u - x) >> 3);                         // rank of this block in its class

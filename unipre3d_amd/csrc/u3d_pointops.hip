@@ -12,7 +12,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "unipre3d_pointops.h"
 
@@ -20,16 +19,9 @@ namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// workgroup sizes of the furthest-point-sampling kernel (experiments: make EXTRA=-DU3D_FPS_BIG_THREADS=512 LIBDIR=../lib_x)
-#ifndef U3D_FPS_SMALL_THREADS
-#define U3D_FPS_SMALL_THREADS 256    // clouds of <= 1024 points
-#endif
-#ifndef U3D_FPS_PK
-#define U3D_FPS_PK 1                 // two points per v_pk_*_f32 instruction in the distance update
-#endif
-#ifndef U3D_FPS_BIG_THREADS
-#define U3D_FPS_BIG_THREADS 1024     // clouds of <= 8192 points
-#endif
+// workgroup sizes of the furthest-point-sampling kernel
+constexpr int FPS_SMALL_THREADS = 256;    // clouds of <= 1024 points
+constexpr int FPS_BIG_THREADS = 1024;     // clouds of <= 8192 points
 
 // `a*a + b*b + c*c` and `w0*p0 + w1*p1 + w2*p2` as the reference's kernels write them (sampling_gpu.cu:140, ball_query_gpu.cu:38,
 // interpolate_gpu.cu:40, :103) are compiled by nvcc with -fmad=true: WHICH product is rounded on its own before the two fused
@@ -60,7 +52,6 @@ __device__ __forceinline__ float dist2(float ax, float ay, float az, float bx, f
   const float dx = bx - ax, dy = by - ay, dz = bz - az;
   return sum3<CM>(dx, dx, dy, dy, dz, dz);
 }
-bool g_interp_lds = getenv("U3D_INTERP_GLOBAL") == nullptr;   // (experiment switch: U3D_INTERP_GLOBAL=1 keeps round 5's global-gather kernel)
 int g_contraction = U3D_PO_FMA_LLVM;   // host: mode of the launches that follow (process-wide, like a build flag of the reference)
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
@@ -142,13 +133,13 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(int n, int m, int lg, 
   for (int j = 1; j < m; ++j) {
     const float ox = s_xyz[old * 3], oy = s_xyz[old * 3 + 1], oz = s_xyz[old * 3 + 2];
     uint32_t lmax = 0u;
-    if constexpr (PPT == 1 || PPT > 4 || !U3D_FPS_PK) {   // (packed math measured 4 % ahead at 4 points per lane, 3 % behind at 8)
+    if constexpr (PPT == 1 || PPT > 4) {   // scalar distance update
 #pragma unroll
       for (int i = 0; i < PPT; ++i) {
         t[i] = min(t[i], __float_as_uint(dist2<CM>(ox, oy, oz, x[i], y[i], z[i])));
         lmax = max(lmax, t[i]);
       }
-    } else {
+    } else {   // two points per v_pk_*_f32 instruction (packed math measured 4 % ahead at 4 points per lane, 3 % behind at 8)
 #pragma unroll
       for (int i = 0; i < PPT; i += 2) {
 #pragma clang fp contract(off)
@@ -588,13 +579,7 @@ __global__ __launch_bounds__(256) void three_interpolate_kernel(int c, int m, in
 // loads, then its stores on the gathers, and 16 K such waves run in two rounds.  Here a workgroup stages IL_CB channel rows of the known
 // cloud in LDS (they are consecutive in memory: one coalesced copy), and every thread interpolates IL_PT points from LDS -- index / weight
 // loads of all its points in flight at once, LDS gathers (~50 clocks instead of an L2 round trip), coalesced stores.  Same sum3, bit-exact.
-#ifndef U3D_IL_CB
-#define U3D_IL_CB 4
-#endif
-#ifndef U3D_IL_PT
-#define U3D_IL_PT 4
-#endif
-constexpr int IL_CB = U3D_IL_CB, IL_PT = U3D_IL_PT;
+constexpr int IL_CB = 4, IL_PT = 4;
 template <int CM>
 __global__ __launch_bounds__(256) void three_interpolate_lds_kernel(int c, int m, int n, const float* __restrict__ points,
                                                                     const int32_t* __restrict__ idx, const float* __restrict__ weight,
@@ -715,22 +700,14 @@ inline int lds_rows(int len, int b, int c) {
   while (cb * 2 <= 16 && cb * 2 <= fit && cb * 2 <= want) cb *= 2;
   return cb;
 }
-// rows per workgroup the two gradient entry points launch with: lds_rows unless the experiment switch (U3D_GG_CB / U3D_IG_CB, read once per
-// process) names another count that fits 64 KB; 0 -- also for a switch value without an instantiation -- is the global-atomic kernel.
-// Host arithmetic only: the u3d_*_grad_rows queries answer through it without touching the device.
-inline int grad_rows(int len, int b, int c, int env) {
-  int cb = lds_rows(len, b, c);
-  if (env > 0 && cb > 0 && (size_t)env * len * sizeof(float) <= 65536) cb = env;
+// rows per workgroup the two gradient entry points launch with: lds_rows, and 0 (the global-atomic kernel) for a count without an
+// instantiation.  Host arithmetic only: the u3d_*_grad_rows queries answer through it without touching the device.
+inline int grad_rows(int len, int b, int c) {
+  const int cb = lds_rows(len, b, c);
   return (cb == 16 || cb == 8 || cb == 4 || cb == 2 || cb == 1) ? cb : 0;
 }
-inline int group_grad_rows(int b, int c, int n) {
-  static const int cb_env = getenv("U3D_GG_CB") ? atoi(getenv("U3D_GG_CB")) : 0;   // (experiment switch)
-  return grad_rows(n, b, c, cb_env);
-}
-inline int interp_grad_rows(int b, int c, int m) {
-  static const int ig_env = getenv("U3D_IG_CB") ? atoi(getenv("U3D_IG_CB")) : 0;   // (experiment switch)
-  return m > 0 ? grad_rows(m, b, c, ig_env) : 0;
-}
+inline int group_grad_rows(int b, int c, int n) { return grad_rows(n, b, c); }
+inline int interp_grad_rows(int b, int c, int m) { return m > 0 ? grad_rows(m, b, c) : 0; }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // launch KERNEL<..., CM> for the process-wide contraction mode
@@ -776,12 +753,12 @@ int u3d_furthest_point_sampling(int b, int n, int m, const float* points, float*
     else if (g_contraction == U3D_PO_FMA_CHAIN) FPS_CM(T, P, U3D_PO_FMA_CHAIN); \
     else FPS_CM(T, P, U3D_PO_NO_FMA);                                \
   } while (0)
-  // small clouds: U3D_FPS_SMALL_THREADS / 64 waves keep the per-selection chain short; larger ones spread over U3D_FPS_BIG_THREADS / 64
-  constexpr int ST = U3D_FPS_SMALL_THREADS, BT = U3D_FPS_BIG_THREADS;
+  // small clouds: FPS_SMALL_THREADS / 64 waves keep the per-selection chain short; larger ones spread over FPS_BIG_THREADS / 64
+  constexpr int ST = FPS_SMALL_THREADS, BT = FPS_BIG_THREADS;
   bool big_lds_refused = false;
   // one wave per cloud up to 512 points (measured, us per selection, one wave / multi-wave: 256 points 0.273 / 0.393, 512: 0.329 / 0.391, 1024: 0.46 - 0.485 /
-  // 0.42 - 0.44, 2048: 0.98 / 0.50: a lone wave issues one VALU instruction per ~3 clocks, 11 per point and selection).  U3D_FPS_WAVE_MAX: experiment switch
-  static const int wave_max = getenv("U3D_FPS_WAVE_MAX") ? atoi(getenv("U3D_FPS_WAVE_MAX")) : 512;
+  // 0.42 - 0.44, 2048: 0.98 / 0.50: a lone wave issues one VALU instruction per ~3 clocks, 11 per point and selection)
+  constexpr int wave_max = 512;
 #define FPSW(P)                                                                                                        \
   do {                                                                                                                 \
     if (g_contraction == U3D_PO_FMA_LLVM) hipLaunchKernelGGL((fps_wave_kernel<P, U3D_PO_FMA_LLVM>), dim3(b), dim3(64), lds, s, n, m, lg, points, idx);        \
@@ -888,7 +865,7 @@ int u3d_three_interpolate(int b, int c, int m, int n, const float* points, const
   if (b == 0 || c == 0 || n == 0) return 0;
   if (b > 65535 || (c + IC_CH - 1) / IC_CH > 65535) return 1;
   if (!points || !idx || !weight || !out) return 1;
-  if (m > 0 && (size_t)m * IL_CB * sizeof(float) <= 32768 && (c + IL_CB - 1) / IL_CB <= 65535 && g_interp_lds) {
+  if (m > 0 && (size_t)m * IL_CB * sizeof(float) <= 32768 && (c + IL_CB - 1) / IL_CB <= 65535) {
     U3D_PO_LAUNCH_CM(three_interpolate_lds_kernel, dim3((n + 256 * IL_PT - 1) / (256 * IL_PT), (c + IL_CB - 1) / IL_CB, b), dim3(256),
                      sizeof(float) * (size_t)m * IL_CB, (hipStream_t)stream, c, m, n, points, idx, weight, out);
   } else {

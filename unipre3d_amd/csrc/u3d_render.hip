@@ -11,8 +11,7 @@
 // tile's rows to a fixed-order f64 reduction (the original: one fp32 atomic per pixel per component, non-deterministic).
 // render_fb_wave_kernel does forward and backward of the fused render-loss training step in a single pass.
 #include "u3d_common.h"
-#if defined(U3D_LPT_EXPERIMENT) || defined(U3D_TIMELINE)
-#include <algorithm>
+#ifdef U3D_TIMELINE
 #include <cstdio>
 #include <vector>
 #endif
@@ -22,9 +21,6 @@ namespace {
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float ALPHA_MIN = 1.0f / 255.0f;
 constexpr float T_STOP = 0.0001f;
-#ifndef U3D_FWD_HOIST
-#define U3D_FWD_HOIST 1      // forward: one wave-uniform saturation test per entry instead of four per-pixel mask chains (round 6)
-#endif
 
 __device__ __forceinline__ bool rect_hits(const uint2 r, int tx, int ty) {
   const int x0 = r.x & 0xffffu, y0 = r.x >> 16, x1 = r.y & 0xffffu, y1 = r.y >> 16;
@@ -80,13 +76,12 @@ __device__ __forceinline__ float mask_sel0(lanemask_t m, float a) {   // lane in
   asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(a), "s"(m));
   return r;
 }
-// m = a & b (NOT_B: a & ~b);  acc |= m;  returns lane in m ? v : 0.
+// m = a & b;  acc |= m;  returns lane in m ? v : 0.
 // (Round 4 tried forming the combined mask IN vcc and selecting with the VOP2 v_cndmask that reads vcc -- 2-cycle class in isolation
 // against 4 for the VOP3 form on an SGPR pair: the scalar write -> vector read of vcc serialises each pixel's chain, render_fb at C2
 // 191.5 -> 198.5 us, compact 641 -> 682 us; EXPERIMENTS.md.)
-template <bool NOT_B>
 __device__ __forceinline__ float mask_combine_sel0(lanemask_t a, lanemask_t b, lanemask_t& acc, float v) {
-  const lanemask_t m = NOT_B ? (a & ~b) : (a & b);
+  const lanemask_t m = a & b;
   acc |= m;
   return mask_sel0(m, v);
 }
@@ -122,9 +117,6 @@ constexpr int BWD_PART_STRIDE = U3D_PART_STRIDE;   // floats per tile: [U3D_PART
 // slice is latency-bound (cost ~ tiles per slice): ~128 tiles per slice measured best (C2: 10.4 us with 2 slices, 17 with 8).
 // With few views (scene level: 8-16) that alone leaves most CUs idle, so the slice count also grows until ~256 workgroups exist.
 static inline int bwd_reduce_split(int T, int NV) {
-#ifdef U3D_REDUCE_SPLIT_ENV   /* experiment builds: slices per view from the environment */
-  if (const char* e = getenv("U3D_REDUCE_SPLIT")) { const int v = atoi(e); if (v > 0 && v <= 32 && v <= T) return v; }
-#endif
   int s = (T + 64) / 128;
   const int fill = NV > 0 ? 256 / NV : 1;
   if (s < fill) s = fill;
@@ -261,10 +253,8 @@ __device__ __forceinline__ bool tile_forward(const TileLds& L, const TileGeom& G
       const float dy = A.y - pyf;
       const float bdy = A.w * dy, cdy2 = (Q.x * dy) * dy;
       lanemask_t contrib = 0ull, m_stop[4];
-      [[maybe_unused]] lanemask_t stopped = 0ull;
       float ar[4];
       if (PLAIN) alpha_run(A.x, A.z, bdy, cdy2, Q.y, L.S[j * L.sstride], pxf[0], ar);
-#if U3D_FWD_HOIST
       // Round 6: the saturation test leaves the per-pixel chains.  A pixel saturates once, and with the reference's large splats the pixels
       // of a tile do so within its last few entries; everywhere else `T (1 - alpha) < 1e-4` is false for all 256 pixels.  So each pixel
       // takes  we = ok ? alpha T : 0,  Tn = T - we  (one compare, one select, no scalar mask algebra), ONE test of the smallest Tn over
@@ -298,7 +288,6 @@ __device__ __forceinline__ bool tile_forward(const TileLds& L, const TileGeom& G
         for (int k = 0; k < 4; ++k) {
           m_stop[k] = __builtin_amdgcn_fcmpf(tn[k], T_STOP, U3D_FCMP_OLT);
           contrib |= m_okv[k] & ~m_stop[k];
-          stopped |= m_stop[k];
           wv[k] = mask_sel(m_stop[k], 0.f, wv[k]);
           tn[k] = F.Tr[k] - wv[k];
         }
@@ -311,38 +300,8 @@ __device__ __forceinline__ bool tile_forward(const TileLds& L, const TileGeom& G
         if (DEPTH) F.Dv[k] = fmaf(invd, wv[k], F.Dv[k]);
         F.Tr[k] = tn[k];
       }
-#else
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {   // one basic block: the four pixels' dependency chains interleave
-        float pw = 0.f;
-        if (!PLAIN) {
-          const float dx = A.x - pxf[k];
-          pw = fmaf(fmaf(A.z, dx, bdy), dx, cdy2);
-          ar[k] = Q.y * __builtin_amdgcn_exp2f(pw);
-        }
-        const float araw = ar[k];
-        const float alpha = PLAIN ? araw : min_099(araw);
-        const lanemask_t m_ok = PLAIN ? __builtin_amdgcn_fcmpf(alpha, amin[k], U3D_FCMP_OGE)
-                                      : __builtin_amdgcn_fcmpf(pw, 0.f, U3D_FCMP_OLE) & __builtin_amdgcn_fcmpf(alpha, amin[k], U3D_FCMP_OGE);
-        const float w = alpha * F.Tr[k];
-        const float test_T = F.Tr[k] - w;          // T (1 - alpha)
-        const lanemask_t m_lt = __builtin_amdgcn_fcmpf(test_T, T_STOP, U3D_FCMP_OLT);
-        m_stop[k] = m_ok & m_lt;
-        const float we = mask_combine_sel0<true>(m_ok, m_lt, contrib, w);   // blended weight (m_ok & ~m_lt), 0 for pixels that skip this Gaussian
-        F.C0[k] = fmaf(Q.z, we, F.C0[k]);
-        F.C1[k] = fmaf(Q.w, we, F.C1[k]);
-        F.C2[k] = fmaf(R.x, we, F.C2[k]);
-        if (DEPTH) F.Dv[k] = fmaf(invd, we, F.Dv[k]);
-        F.Tr[k] -= we;
-        stopped |= m_stop[k];
-      }
-#endif
       if (contrib != 0ull) { jlast = j; blast = b; }
-#if U3D_FWD_HOIST
       if (some_stop) {         // wave-uniform: pixels saturating at this Gaussian (the last few entries of a tile's walk)
-#else
-      if (stopped != 0ull) {   // rare, wave-uniform: pixels saturating at this Gaussian
-#endif
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           amin[k] = mask_sel(m_stop[k], 2.f, amin[k]);
@@ -426,7 +385,7 @@ __device__ __forceinline__ void tile_backward(const TileLds& L, const TileGeom& 
         const lanemask_t m_a = (PLAIN ? ~0ull : __builtin_amdgcn_fcmpf(pw, 0.f, U3D_FCMP_OLE)) & __builtin_amdgcn_fcmpf(araw, ALPHA_MIN, U3D_FCMP_OGE);
         // (Round 6 tried skipping the `pos < lim` compares for entries in front of the tile's EARLIEST limit -- a wave-uniform test per entry,
         //  true for most of the walk: +3 % at C2 / C3, +1.7 % at C5.  The scalar branch costs more than the four compares and s_and it saves.)
-        ae[k] = mask_combine_sel0<false>(m_a, __builtin_amdgcn_uicmp(pos, lim[k], U3D_ICMP_ULT), any, araw);
+        ae[k] = mask_combine_sel0(m_a, __builtin_amdgcn_uicmp(pos, lim[k], U3D_ICMP_ULT), any, araw);
       }
       if (any == 0ull) continue;
       float m0, mx, mxx, g_r, g_g, g_b, g_d = 0.f;
@@ -613,27 +572,12 @@ __device__ __forceinline__ void store4(float* __restrict__ p, bool vec, const bo
 // taken variant) 3 % ahead of the unpinned build; with round 5's alpha_run and round 6's forward the optimum moved to 7 (72 VGPRs, fewer spills):
 // render_fb scope, pins 8 / 7 / 6 / none on one box, two rounds: C2 176.0 / 173.2 - 173.7 / 176.1 - 176.3 / 177.2 - 177.5 us, C3 91.8 - 92.4 / 90.5 - 91.0 /
 // 92.1 - 92.2 / 92.3, C5 103.3 - 103.8 / 101.4 - 101.5 / 100.7 - 101.0 / 101.0 - 101.5.  The two-pass kernels measured slower pinned to 8 (forward 97 against
-// 87 us at C2); the forward is left to the allocator (61 / 66 VGPRs), the backward's object-level instantiation takes 7 (see U3D_BWD_OCC_PIN).
-#ifdef U3D_NO_OCC_PIN   /* tools/pmc_spill_probe.sh: the unpinned build, to attribute the scratch-spill share of the kernel's HBM writes */
-#define U3D_FULL_OCCUPANCY
-#else
-#ifndef U3D_OCC_PIN
-#define U3D_OCC_PIN 7
-#endif
-#define U3D_FULL_OCCUPANCY __attribute__((amdgpu_waves_per_eu(U3D_OCC_PIN, U3D_OCC_PIN)))
-#endif
+// 87 us at C2); the forward is left to the allocator (61 / 66 VGPRs), the backward's object-level instantiation takes 7 (see U3D_BWD_OCCUPANCY).
+#define U3D_FULL_OCCUPANCY __attribute__((amdgpu_waves_per_eu(7, 7)))
 // Grid = (T tiles of a view, views [, view slabs of 65535]): the view index comes from the block id, the tile row from a host-made
 // magic multiplier (`tile_magic`, 0 = divide), so the prologue has no integer division.  Workgroups are dispatched to the XCDs
 // round-robin in linear order x + T * view, which is what u3d_xcd_chunk_in_view assumes.
 static_assert(TILE_WAVES == 1, "one wave = one workgroup = one tile");
-#ifdef U3D_LPT_EXPERIMENT   /* tools/lpt_tiles.sh: tiles dispatched in the order of a host-made permutation (cost of the previous, identical step) */
-__device__ uint32_t* g_lpt_perm = nullptr;
-__device__ uint32_t* g_lpt_cost = nullptr;
-#define U3D_LPT_MAP                                                                                     \
-  if (g_lpt_perm) { const uint32_t lin_ = g_lpt_perm[blockIdx.x + (uint32_t)T * view_u]; view_u = lin_ / (uint32_t)T; tile = (int)(lin_ - view_u * (uint32_t)T); }
-#else
-#define U3D_LPT_MAP
-#endif
 #ifdef U3D_TIMELINE   /* tools/tile_timeline.sh: when and where (XCD, CU, SIMD, wave slot) every tile of a launch ran */
 __device__ uint4* g_timeline = nullptr;   // two uint4 per tile
 #endif
@@ -642,7 +586,6 @@ __device__ uint4* g_timeline = nullptr;   // two uint4 per tile
   uint32_t view_u = blockIdx.y + gridDim.y * blockIdx.z;                                                \
   if (view_u * (uint32_t)T >= ntiles_total) return; /* (partial last slab) */                           \
   int tile = (int)u3d_xcd_chunk_in_view(blockIdx.x, view_u, (uint32_t)T, span.P <= 256 ? view_u : 0u);  \
-  U3D_LPT_MAP                                                                                           \
   const int view = (int)view_u;                                                                         \
   const uint32_t lid = view_u * (uint32_t)T + (uint32_t)tile;                                           \
   const int ty = tile_magic ? (int)__umulhi((uint32_t)tile, tile_magic) : tile / tiles_x;               \
@@ -721,15 +664,8 @@ __global__ __launch_bounds__(TILE_WAVES * U3D_WAVE) void render_fwd_wave_kernel(
 // ---- backward (operator path, and second pass of the two-pass fused loss) ------------------------------------
 // Occupancy: the allocator gives this kernel 76 VGPRs = 6 waves per SIMD.  Round 6: the object-level instantiation without inverse-depth gradients (PB == 1, !HAS_INVD: what the reference's call produces) is pinned to 7 (72 VGPRs,
 // 20 B of scratch per lane) like the single-pass kernel: two-pass route, render_bwd 161.0 -> 156.2 us at C2 in two alternating pairs; the scene-level
-// one (PB == 2) measured -0.8 % at C3 but +1.6 % at C5 pinned and is left to the allocator (1 .. 10 = no constraint).  U3D_BWD_OCC_PIN=0: no pin at all.
-#ifndef U3D_BWD_OCC_PIN
-#define U3D_BWD_OCC_PIN 7
-#endif
-#if U3D_BWD_OCC_PIN
-#define U3D_BWD_OCCUPANCY __attribute__((amdgpu_waves_per_eu((PB == 1 && !HAS_INVD) ? U3D_BWD_OCC_PIN : 1, (PB == 1 && !HAS_INVD) ? U3D_BWD_OCC_PIN : 10)))
-#else
-#define U3D_BWD_OCCUPANCY
-#endif
+// one (PB == 2) measured -0.8 % at C3 but +1.6 % at C5 pinned and is left to the allocator (1 .. 10 = no constraint).
+#define U3D_BWD_OCCUPANCY __attribute__((amdgpu_waves_per_eu((PB == 1 && !HAS_INVD) ? 7 : 1, (PB == 1 && !HAS_INVD) ? 7 : 10)))
 template <bool HAS_INVD, int PB>
 __global__ __launch_bounds__(TILE_WAVES * U3D_WAVE) U3D_BWD_OCCUPANCY void render_bwd_wave_kernel(
     U3DSpan span, int H, int W, int tiles_x, int T, uint32_t ntiles_total, uint32_t tile_magic, size_t NG,
@@ -822,9 +758,6 @@ __global__ __launch_bounds__(TILE_WAVES * U3D_WAVE) U3D_FULL_OCCUPANCY void rend
 #ifdef U3D_TIMELINE
   const uint64_t tl_t0 = __builtin_amdgcn_s_memrealtime(), tl_c0 = __builtin_amdgcn_s_memtime();
 #endif
-#ifdef U3D_PRIO_FWD
-  __builtin_amdgcn_s_setprio(U3D_PRIO_FWD);
-#endif
   U3D_TILE_PROLOGUE(TILE_WAVES);
   const TileLds L{sP0[wave], sP1[wave], sP2[wave], nullptr, sAcc[wave], &sAcc[wave][0][9], 10};
 #pragma unroll
@@ -865,14 +798,8 @@ __global__ __launch_bounds__(TILE_WAVES * U3D_WAVE) U3D_FULL_OCCUPANCY void rend
   }
   e = u3d_wave_sum(e);
   if (lane == 0) loss.partial[lid] = e;
-#ifdef U3D_LPT_EXPERIMENT
-  if (lane == 0 && g_lpt_cost) g_lpt_cost[lid] = F.wlast;
-#endif
 #ifdef U3D_TIMELINE
   const uint64_t tl_t2 = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef U3D_PRIO_BWD
-  __builtin_amdgcn_s_setprio(U3D_PRIO_BWD);
 #endif
 
   if (plain)
@@ -901,10 +828,9 @@ __global__ __launch_bounds__(TILE_WAVES * U3D_WAVE) U3D_FULL_OCCUPANCY void rend
 // One thread per (position, component) element of a tile's [64][10] block, so a tile is one contiguous read; only the
 // positions some tile of the slice touched (cmax, usually ~20 of 64) are read at all.
 constexpr int REDUCE_THREADS = U3D_WAVE * 10;
-// tiles in flight per thread: 32 in the single-block kernel (object level), 16 in the generic one (measured, tools/sweep_ru.sh:
+// tiles in flight per thread: 32 in the single-block kernel (object level), 16 in the generic one (measured:
 // C3 10.1 -> 9.3 us, C4 17.0 -> 15.5, C5 13.0 -> 11.8 with 16; C2 11.3 -> 11.6; 64 is slower everywhere)
-#define RU 16
-#define RU1 32
+constexpr int RU = 16, RU1 = 32;
 template <int PB>
 __global__ __launch_bounds__(REDUCE_THREADS) void bwd_reduce_kernel(U3DSpan span, int T, int NK, int nsplit, size_t NG, float half_w, float half_h,
                                                                    const uint32_t* __restrict__ sorted_id,
@@ -1190,46 +1116,6 @@ void u3d_launch_render_fb(const u3d_raster_desc& d, const U3DBuffers& b, const f
   uint32_t* tw = u3d_uses_touched_words(d) ? b.touched_words : nullptr;
   uint2* tl = (list_touched && tw) ? b.touched_list : nullptr;
   uint32_t* tc = (list_touched && tw) ? b.touched_count : nullptr;
-#ifdef U3D_LPT_EXPERIMENT
-  {
-    static int launches = 0;
-    static uint32_t *d_cost = nullptr, *d_perm = nullptr;
-    static const int mode = getenv("U3D_LPT_MODE") ? atoi(getenv("U3D_LPT_MODE")) : 0;   // 1 heavy first, 2 light first, 3 random (control), 4 heavy first within views interleaved
-    if (mode > 0 && u3d_part_blocks(d) == 1) {
-      ++launches;
-      if (launches == 1) {
-        (void)hipMalloc(&d_cost, sizeof(uint32_t) * ntiles); (void)hipMalloc(&d_perm, sizeof(uint32_t) * ntiles);
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lpt_cost), &d_cost, sizeof(d_cost));
-      }
-      if (launches == 30) {
-        (void)hipStreamSynchronize(s);
-        std::vector<uint32_t> cost(ntiles), perm(ntiles);
-        (void)hipMemcpy(cost.data(), d_cost, sizeof(uint32_t) * ntiles, hipMemcpyDeviceToHost);
-        for (uint32_t i = 0; i < ntiles; ++i) perm[i] = i;
-        if (mode == 1) std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-        if (mode == 2) std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return cost[a] < cost[b]; });
-        if (mode == 3) { uint32_t st = 12345u; for (uint32_t i = ntiles - 1; i > 0; --i) { st = st * 1664525u + 1013904223u; std::swap(perm[i], perm[st % (i + 1)]); } }
-        if (mode == 4) {   // per view: its tiles heavy first; block b -> (view b % NV, rank b / NV): what a production form could compute per view
-          const uint32_t NV = ntiles / (uint32_t)T;
-          std::vector<uint32_t> within(ntiles);
-          for (uint32_t v = 0; v < NV; ++v) {
-            std::vector<uint32_t> t((size_t)T);
-            for (int j = 0; j < T; ++j) t[j] = v * (uint32_t)T + (uint32_t)j;
-            std::stable_sort(t.begin(), t.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-            for (int j = 0; j < T; ++j) within[v * (uint32_t)T + (uint32_t)j] = t[j];
-          }
-          for (uint32_t b2 = 0; b2 < ntiles; ++b2) perm[b2] = within[(b2 % NV) * (uint32_t)T + b2 / NV];
-        }
-        double mean = 0; uint32_t mx = 0; for (auto c2 : cost) { mean += c2; mx = c2 > mx ? c2 : mx; }
-        fprintf(stderr, "[lpt] mode %d: %u tiles, cost mean %.2f max %u; first %u last %u\n", mode, ntiles, mean / ntiles, mx, cost[perm[0]], cost[perm[ntiles - 1]]);
-        (void)hipMemcpy(d_perm, perm.data(), sizeof(uint32_t) * ntiles, hipMemcpyHostToDevice);
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lpt_perm), &d_perm, sizeof(d_perm));
-        uint32_t* nul = nullptr;
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_lpt_cost), &nul, sizeof(nul));
-      }
-    }
-  }
-#endif
 #ifdef U3D_TIMELINE
   {
     static int launches = 0;
