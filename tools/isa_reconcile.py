@@ -14,9 +14,10 @@ cost = {c["op"]: c["cycles_per_slot_at_2_per_fma"] for c in costs}
 
 loops = hist["loops"]
 nd = lambda lp, k: lp["valu_subclasses"].get(k, 0)
-# backward PLAIN body: the loop with the 26 DPP adds of the reduction and the fewest transcendentals (2 exp2 of alpha_run + 4 rcp); its
-# inner "skip" loop (entries that contribute nothing to the tile) is the one it contains with LDS reads and no DPP
-bwd = min((lp for lp in loops if nd(lp, "dpp") == 26), key=lambda lp: (nd(lp, "trans"), lp["instructions"]))
+# backward PLAIN body: the loop with the 20 DPP adds of the reduction (14 bank-masked on the raw values, 6 quad-level on the packed registers) and
+# the fewest transcendentals (2 exp2 of alpha_run + 4 rcp); its inner "skip" loop (entries that contribute nothing to the tile) is the one it
+# contains with LDS reads and no DPP
+bwd = min((lp for lp in loops if nd(lp, "dpp") == 20), key=lambda lp: (nd(lp, "trans"), lp["instructions"]))
 # forward PLAIN body: no DPP, one v_min3 (the hoisted saturation test), 2 transcendentals, the smallest such loop with LDS reads
 fwd = min((lp for lp in loops if nd(lp, "dpp") == 0 and "v_min3_f32" in lp["opcodes"] and nd(lp, "trans") == 2 and lp["classes"].get("LDS", 0) >= 3),
           key=lambda lp: lp["instructions"])

@@ -105,13 +105,19 @@ __device__ __forceinline__ float min_099(float a) {   // fminf(0.99f, a) without
 //   * exponent  pw = (a' dx + b' dy) dx + c' dy^2  with the -log2e/2 factors folded in at staging (3 ops/pixel);
 //   * compare results live as lane masks on the scalar unit; a pixel that skips a Gaussian takes the same straight-line
 //     code with its weight selected to zero (no per-pixel branches, four dependency chains per basic block);
-//   * backward: with  R_i = sum_{j behind i} w_j (c_j . dL/dC) + T_final (bg . dL/dC)
-//         dL/dalpha_i = T_i (c_i . dL/dC) - R_i / (1 - alpha_i),      R_{i-1} = R_i + w_i (c_i . dL/dC),
-//     the same quantity as the reference's normalised "accum_rec" form in three instructions and one running value;
-//   * only m0, mx, mxx and the colour (depth) gradients are accumulated per pixel; after the two quad levels of the
-//     reduction  my = dy m0, mxy = dy mx, myy = dy my;
-//   * the half-row and row levels use DPP bank masks to deposit two values into one register per instruction pair
-//     (9-10 values -> 5 -> 3 registers), and the four rows of the wave meet through the LDS crossbar (swizzle + bpermute).
+//   * backward: with  R_i = sum_{j behind i} w_j (c_j . dL/dC) + T_final (bg . dL/dC)  and  T_{i+1} = T_i (1 - alpha_i),
+//     the walk keeps the NORMALISED remainder  rho_i = R_i / T_{i+1}  (the colour the pixel would show behind entry i, dotted
+//     with dL/dC; behind the last entry it is bg . dL/dC):
+//         d_i = c_i . dL/dC - rho_i,    dL/dalpha_i = T_i d_i,    rho_{i-1} = rho_i + alpha_i d_i,
+//     i.e. dL/dalpha_i = T_i (c_i . dL/dC) - R_i / (1 - alpha_i) with one subtraction, one FMA and one multiply.  The update is
+//     convex (rho stays between the colours it has seen), so nothing grows where T_final is ~1e-4; a pixel outside the image
+//     has Tr = 0, hence T_i = w = q = 0 whatever rho is;
+//   * per pixel only q = dL/dG * G and the colour (depth) gradients are formed; a lane's pixels are dx0 - k, so its moments
+//     m0, mx, mxx come from q_0..q_3 and the run's centre, and  my = dy m0, mxy = dy mx, myy = dy my  per lane (a quad
+//     shares dy) before any cross-lane step;
+//   * the half-row and row levels come first and use DPP bank masks to deposit two values into one register per
+//     instruction pair (9-10 values -> 5 -> 3 registers), the two quad levels then run on the 3 packed registers, and the
+//     four rows of the wave meet through the LDS crossbar (swizzle + bpermute).
 constexpr int BWD_PART_STRIDE = U3D_PART_STRIDE;   // floats per tile: [U3D_PART_BLOCKS][64 positions][10], the LDS rows as they are
 // bwd_reduce_kernel: workgroups per view.  The slices of a view meet in f64 atomics (cost ~ slices), the tile chain of a
 // slice is latency-bound (cost ~ tiles per slice): ~128 tiles per slice measured best (C2: 10.4 us with 2 slices, 17 with 8).
@@ -342,7 +348,7 @@ __device__ __forceinline__ T moment_to_acc(int k, const T* m, float a, float b, 
 // part[tile][position][10] (the LDS rows as they are, only the rows the tile touched) and summed over the tiles in a FIXED order, in f64, by
 // bwd_reduce_kernel.  Only sorted positions beyond those blocks (sparse / semi-transparent scenes) fall back to f64 global atomics,
 // whose ordering does not show at fp32 output precision (the original: one fp32 atomic per pixel and component).
-//   Tr = T_final, Rk = T_final (bg . dL/dC), lim = exclusive sorted-position limit per pixel (0: pixel takes no part).
+//   Tr = T_final, Rk = bg . dL/dC (the normalised remainder behind the last entry), lim = exclusive sorted-position limit per pixel (0: pixel takes no part).
 template <bool HAS_INVD, int PB /* partial-row blocks in use */, bool PLAIN /* every batch of the tile qualified in the forward pass */>
 __device__ __forceinline__ void tile_backward(const TileLds& L, const TileGeom& G, int lane, uint32_t wmax, int staged,
                                               lanemask_t staged_bal, float pyf, const float (&pxf)[4],
@@ -388,7 +394,7 @@ __device__ __forceinline__ void tile_backward(const TileLds& L, const TileGeom& 
         ae[k] = mask_combine_sel0(m_a, __builtin_amdgcn_uicmp(pos, lim[k], U3D_ICMP_ULT), any, araw);
       }
       if (any == 0ull) continue;
-      float m0, mx, mxx, g_r, g_g, g_b, g_d = 0.f;
+      float m0, mx, mxx, g_r, g_g, g_b, g_d = 0.f, q[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float alpha = PLAIN ? ae[k] : min_099(ae[k]);
@@ -399,50 +405,38 @@ __device__ __forceinline__ void tile_backward(const TileLds& L, const TileGeom& 
         Tr[k] = Tn;
         float cdp = fmaf(R.x, dp2[k], fmaf(Q.w, dp1[k], Q.z * dp0[k]));
         if (HAS_INVD) cdp = fmaf(invd, dinv[k], cdp);
-        const float dL_dalpha = fmaf(Tn, cdp, -(Rk[k] * rc));
-        Rk[k] = fmaf(w, cdp, Rk[k]);
-        const float q = ae[k] * dL_dalpha;    // dL/dG * G
-        const float qdx = q * dx[k];
+        const float dl = cdp - Rk[k];           // dL/dalpha = T_i dl
+        Rk[k] = fmaf(alpha, dl, Rk[k]);         // convex step towards c . dL/dC: the remainder in front of this Gaussian
+        q[k] = PLAIN ? w * dl : ae[k] * (Tn * dl);   // dL/dG * G  (PLAIN: ae == alpha, so ae T_i = w)
         if (k == 0) {
           g_r = w * dp0[k]; g_g = w * dp1[k]; g_b = w * dp2[k];
           if (HAS_INVD) g_d = w * dinv[k];
-          m0 = q; mx = qdx; mxx = qdx * dx[k];
         } else {
           g_r = fmaf(w, dp0[k], g_r); g_g = fmaf(w, dp1[k], g_g); g_b = fmaf(w, dp2[k], g_b);
           if (HAS_INVD) g_d = fmaf(w, dinv[k], g_d);
-          m0 += q; mx += qdx;
-          mxx = fmaf(qdx, dx[k], mxx);
         }
       }
-      // quad levels (one tile row of 16 pixels per quad); v_add_f32_dpp by hand: hipcc does not fuse update_dpp + fadd
-      // (-0.0 rule).  Dependent DPP ops stay >= 2 instructions apart (VALU write -> DPP read hazard).
-      asm volatile("s_nop 1\n\t"
-                   "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %3, %3, %3 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %4, %4, %4 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %5, %5, %5 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %3, %3, %3 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %4, %4, %4 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_add_f32_dpp %5, %5, %5 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                   "s_nop 1"
-                   : "+v"(m0), "+v"(mx), "+v"(mxx), "+v"(g_r), "+v"(g_g), "+v"(g_b));
-      if (HAS_INVD)
-        asm volatile("s_nop 1\n\t"
-                     "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                     "s_nop 1"
-                     : "+v"(g_d));
+      // the lane's moments over its run dx_k = dc + (1.5 - k), centred so that the offsets are +-1.5, +-0.5:
+      //   mx = dc m0 - t1,  mxx = dc^2 m0 - 2 dc t1 + t2,   t1 = sum q_k (k - 1.5),  t2 = sum q_k (k - 1.5)^2
+      {
+        const float dc = dx[0] - 1.5f;
+        const float s03 = q[0] + q[3], s12 = q[1] + q[2];
+        const float t1 = fmaf(1.5f, q[3] - q[0], 0.5f * (q[2] - q[1]));
+        const float t2 = fmaf(2.25f, s03, 0.25f * s12);
+        m0 = s03 + s12;
+        mx = fmaf(dc, m0, -t1);
+        mxx = fmaf(dc, mx - t1, t2);
+      }
+      // dy is the lane's own (a quad is one tile row), so the dy moments are taken before any lane meets another
       float my = dy * m0, mxy = dy * mx;
       float myy = dy * my;
-      // half-row level (lanes i <-> 7-i: banks 0<->1, 2<->3), two values per register: banks {0,2} keep the first
+      // v_add_f32_dpp by hand: hipcc does not fuse update_dpp + fadd (-0.0 rule).  Dependent DPP ops stay >= 2 instructions
+      // apart (VALU write -> DPP read hazard).
+      // Half-row level first (lanes i <-> 7-i: banks 0<->1, 2<->3), two values per register: banks {0,2} keep the first
       // operand's sums, banks {1,3} receive the second's; then the row level (i <-> i+8: banks 0<->2, 1<->3) the same way:
       //   mx  <- {mx, my, mxx, mxy}    myy <- {myy, m0, g_r, g_g}    g_b <- {g_b, g_d, g_b, g_d}     (bank index = component)
+      // After them lane l of a bank holds the partial sum of lanes {l, 7-l, l+8, 15-l} of its component, and the two quad
+      // levels, which stay inside a bank, finish the 16-lane sums on the three packed registers (6 DPP, not 12 on six).
       if (HAS_INVD)
         asm volatile("s_nop 1\n\t"
                      "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"
@@ -482,6 +476,16 @@ __device__ __forceinline__ void tile_backward(const TileLds& L, const TileGeom& 
                      "s_nop 1"
                      : "+v"(mx), "+v"(mxx), "+v"(myy), "+v"(g_r), "+v"(g_b)
                      : "v"(my), "v"(mxy), "v"(m0), "v"(g_g));
+      // quad levels (lanes of one bank) on the packed registers
+      asm volatile("s_nop 1\n\t"
+                   "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                   "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                   "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                   "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                   "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                   "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+                   "s_nop 1"
+                   : "+v"(mx), "+v"(myy), "+v"(g_b));
       // the four 16-lane rows meet in LDS: batch 0 is indexed by sorted position (merged across tiles by
       // bwd_reduce_kernel), later batches by compaction slot
       const uint32_t slot = b < PB ? pos - 1u - (uint32_t)(b * U3D_WAVE) : (uint32_t)j;
@@ -726,7 +730,7 @@ __global__ __launch_bounds__(TILE_WAVES * U3D_WAVE) U3D_BWD_OCCUPANCY void rende
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     lim[k] = __float_as_uint(limf[k]);
-    Rk[k] = Tr[k] * (bg[0] * dp0[k] + bg[1] * dp1[k] + bg[2] * dp2[k]);   // T_final * (bg . dL/dC)
+    Rk[k] = bg[0] * dp0[k] + bg[1] * dp1[k] + bg[2] * dp2[k];   // bg . dL/dC
   }
   const uint32_t tl = tile_last[lid];
   if (tl & U3D_TILE_PLAIN_BIT)
@@ -794,7 +798,7 @@ __global__ __launch_bounds__(TILE_WAVES * U3D_WAVE) U3D_FULL_OCCUPANCY void rend
     loss_seed(lc, wk, loss.inv_count, d0, d1, d2, dp0[k], dp1[k], dp2[k]);   // dL/dloss == 1
     dinv[k] = 0.f;
     F.Tr[k] = inside[k] ? F.Tr[k] : 0.f;
-    Rk[k] = F.Tr[k] * (bg[0] * dp0[k] + bg[1] * dp1[k] + bg[2] * dp2[k]);   // T_final * (bg . dL/dC)
+    Rk[k] = bg[0] * dp0[k] + bg[1] * dp1[k] + bg[2] * dp2[k];   // bg . dL/dC
   }
   e = u3d_wave_sum(e);
   if (lane == 0) loss.partial[lid] = e;
