@@ -160,6 +160,12 @@ def ptr(t) -> ctypes.c_void_p:
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+def scratch(nbytes: int, dev):
+    """(tensor that owns the bytes, 256-byte aligned device pointer into it)."""
+    buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+    return buf, ctypes.c_void_p((buf.data_ptr() + 255) & ~255)
+
+
 def profile_begin(max_records: int = 65536, kinds=None, stride: int = 1) -> None:
     """kinds: iterable of PROFILE_KINDS names to record (None = all); stride: sample every stride-th launch of a kind (1..15).
     Each recorded scope costs ~4-5 us on the stream."""

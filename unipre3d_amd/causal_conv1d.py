@@ -43,12 +43,6 @@ def chunk_len(L: int) -> int:
     return int(load().u3d_cconv_chunk_len(int(L)))
 
 
-def scratch(nbytes: int, dev):
-    """(tensor that owns the bytes, 256-byte aligned device pointer into it)."""
-    buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    return buf, ctypes.c_void_p((buf.data_ptr() + 255) & ~255)
-
-
 class _CausalConv1d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, silu):
@@ -72,7 +66,7 @@ class _CausalConv1d(torch.autograd.Function):
         dweight = torch.empty_like(weight)
         dbias = torch.empty_like(bias) if bias is not None else None
         nbytes = int(lib.u3d_cconv_bwd_scratch_bytes(Bsz, D))
-        buf, base = scratch(nbytes, x.device)
+        buf, base = _lib.scratch(nbytes, x.device)
         p = _lib.ptr
         check(lib.u3d_cconv_bwd(p(x), p(weight), p(bias), p(dout), p(dx), p(dweight), p(dbias), base, nbytes, x.stride(0), x.stride(1),
                                 Bsz, D, L, weight.shape[1], int(ctx.silu), stream_ptr(x.device)), "u3d_cconv_bwd", named=False)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "u3d_util.h"
 #include "unipre3d_rasterizer.h"
 
 #define U3D_TILE 16
@@ -182,7 +183,7 @@ static inline size_t u3d_carve_fused(const u3d_raster_desc& d, void* base, U3DFu
 // blocks actually used: one when the whole sorted list fits in it anyway or is short (object level), two otherwise
 static inline int u3d_part_blocks(const u3d_raster_desc& d) { return d.P <= 256 ? 1 : U3D_PART_BLOCKS; }
 #define U3D_PART_STRIDE (U3D_PART_BLOCKS * U3D_WAVE * 10)   // floats per tile
-static inline size_t u3d_align(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline size_t u3d_align(size_t x) { return u3d_util::align256(x); }
 
 // single source of truth for carving; base pointers may be null when only sizes are wanted
 static inline U3DLayout u3d_carve(const u3d_raster_desc& d, void* geom, void* binning, void* image, U3DBuffers* b) {

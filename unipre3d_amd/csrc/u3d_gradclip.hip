@@ -7,8 +7,11 @@
 #include <stdint.h>
 
 #include "unipre3d_gradclip.h"
+#include "u3d_util.h"
 
 namespace {
+
+using namespace u3d_util;
 
 constexpr int GC_THREADS = 512;
 struct __attribute__((aligned(16))) Partial { double sumsq; float amax; uint32_t bad; };
@@ -143,8 +146,6 @@ __global__ __launch_bounds__(GC_THREADS) void gc_scale_kernel(float* const* __re
   if ((int)threadIdx.x < head) p[threadIdx.x] *= coef;
   if (tail0 + (int)threadIdx.x < cnt) p[tail0 + threadIdx.x] *= coef;
 }
-
-int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
 
 }  // namespace
 

@@ -21,8 +21,11 @@
 #include <stdint.h>
 
 #include "unipre3d_mambaops.h"
+#include "u3d_util.h"
 
 namespace {
+
+using namespace u3d_util;
 
 constexpr int NT = 256;                   // threads per workgroup (four waves)
 constexpr int NW = NT / 64;
@@ -33,33 +36,14 @@ constexpr int ROWS_PER_WAVE = 4;          // norm backward: rows a wave owns bef
 constexpr int MAX_BWD_WAVES = 2048;       // ... up to this many (two per SIMD of 256 CUs); beyond it the runs grow
 constexpr int RT = 1024;                  // threads of the norm's reduce workgroup (16 waves over 64 columns)
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-inline int steps_per_lane(int L) { return L <= 64 ? 1 : L <= 128 ? 2 : L <= 192 ? 3 : 4; }
 inline int bwd_waves(int M) {
   if (M < 1) return 0;
   const int want = (M + ROWS_PER_WAVE - 1) / ROWS_PER_WAVE;
   return want < MAX_BWD_WAVES ? want : MAX_BWD_WAVES;
 }
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f(float old, float v) {   // lanes without a source (or outside ROW_MASK) keep `old`
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
 __device__ __forceinline__ float from_below(float edge, float v) { return dpp_f<0x138, 0xf>(edge, v); }   // wave_shr:1, lane 0 := edge
 __device__ __forceinline__ float from_above(float edge, float v) { return dpp_f<0x130, 0xf>(edge, v); }   // wave_shl:1, lane 63 := edge
-template <int LANE>
-__device__ __forceinline__ float lane_f(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), LANE)); }
-__device__ __forceinline__ float wave_sum(float v) {              // the sum of the 64 lanes, in one fixed order, in every lane
-  v += dpp_f<0x111, 0xf>(0.f, v);   // row_shr:1
-  v += dpp_f<0x112, 0xf>(0.f, v);   // row_shr:2
-  v += dpp_f<0x114, 0xf>(0.f, v);   // row_shr:4
-  v += dpp_f<0x118, 0xf>(0.f, v);   // row_shr:8
-  v += dpp_f<0x142, 0xa>(0.f, v);   // row_bcast:15 into rows 1 and 3
-  v += dpp_f<0x143, 0xc>(0.f, v);   // row_bcast:31 into rows 2 and 3
-  return lane_f<63>(v);
-}
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---- causal conv ---------------------------------------------------------------------------------------------------------------------
 struct ConvArgs {
@@ -388,8 +372,6 @@ __global__ __launch_bounds__(RT) void addnorm_reduce_kernel(const double* dwp, c
     if (db) db[n] = (float)b;
   }
 }
-
-inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 // V = 4 where N and every pointer allow 16-byte accesses; NJ = the 64-lane groups a row needs, rounded up to an instantiated count
 template <bool BWD>

@@ -8,8 +8,11 @@
 #include <algorithm>
 
 #include "unipre3d_pointfusion.h"
+#include "u3d_util.h"
 
 namespace {
+
+using namespace u3d_util;
 
 constexpr int NT = 256;              // threads per workgroup (four waves)
 constexpr int NW = NT / 64;
@@ -18,7 +21,6 @@ constexpr int TILE = NT * ITEMS;     // elements per workgroup in the tiled pass
 constexpr int SCAN_NT = 1024;        // the one-workgroup exclusive scan
 
 inline int n_tiles(int n) { return (n + TILE - 1) / TILE; }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // passes of the 8-bit LSD sort: eight over the 64-bit key, then enough over the set index to order sets (0 for one set)
 inline int set_passes(int S) { int q = 0; while (q < 4 && (1ll << (8 * q)) < S) ++q; return q; }
 inline int final_buffer(int S) { return (8 + set_passes(S)) & 1; }
@@ -90,8 +92,6 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {   //
   z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
   return z ^ (z >> 31);
 }
-
-__device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
 
 // ---- min / max corner ------------------------------------------------------------------------------------------------------
 __global__ void minmax_init_kernel(int S, int* __restrict__ mm) {
@@ -264,23 +264,6 @@ __global__ __launch_bounds__(NT) void radix_hist_kernel(int pass, const int32_t*
 // Exclusive scan of one digit's row of tile counts (digit-major layout: one workgroup per digit, coalesced), its total to tot[digit];
 // the scatter adds the exclusive prefix of the 256 totals.  (One workgroup scanning all 256 x tiles entries took ~0.1 ms per pass at
 // 2.4 M points.)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* wt, uint32_t& all) {   // NT threads, wt: NW words of LDS
-  const uint32_t lane = lane_id();
-  const int wave = threadIdx.x >> 6;
-  uint32_t inc = x;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = (uint32_t)__shfl_up((int)inc, o);
-    if ((int)lane >= o) inc += u;
-  }
-  if (lane == 63) wt[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0;
-  all = 0;
-  for (int w = 0; w < NW; ++w) { if (w < wave) before += wt[w]; all += wt[w]; }
-  __syncthreads();
-  return before + inc - x;
-}
-
 __global__ __launch_bounds__(NT) void row_scan_kernel(int nb, uint32_t* __restrict__ hist, uint32_t* __restrict__ tot) {
   __shared__ uint32_t wt[NW];
   uint32_t* row = hist + (size_t)blockIdx.x * nb;
@@ -289,7 +272,7 @@ __global__ __launch_bounds__(NT) void row_scan_kernel(int nb, uint32_t* __restri
     const int b = b0 + threadIdx.x;
     const uint32_t x = b < nb ? row[b] : 0u;
     uint32_t all;
-    const uint32_t e = block_excl_scan(x, wt, all);
+    const uint32_t e = block_excl_scan<NW>(x, wt, all);
     if (b < nb) row[b] = carry + e;
     carry += all;
   }
@@ -311,7 +294,7 @@ __global__ __launch_bounds__(NT) void radix_scatter_kernel(int pass, const int32
   const int tid = threadIdx.x, wave = tid >> 6;
   const uint32_t lane = lane_id();
   uint32_t all;
-  digit_base[tid] = block_excl_scan(tot[tid], wt, all) + hist[(size_t)tid * nb + blockIdx.x];
+  digit_base[tid] = block_excl_scan<NW>(tot[tid], wt, all) + hist[(size_t)tid * nb + blockIdx.x];
   for (int r = 0; r < ITEMS; ++r) {
     for (int w = 0; w < NW; ++w) wave_cnt[w][tid] = 0;
     __syncthreads();
@@ -455,9 +438,6 @@ __global__ __launch_bounds__(NT) void gather_bwd_kernel(int V, int C, int HW, co
     }
   }
 }
-
-inline int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-inline int blocks(long long n, int per) { return (int)((n + per - 1) / per); }
 
 }  // namespace
 

@@ -14,8 +14,11 @@
 #include <stdint.h>
 
 #include "unipre3d_pointops.h"
+#include "u3d_util.h"
 
 namespace {
+
+using namespace u3d_util;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -708,7 +711,6 @@ inline int grad_rows(int len, int b, int c) {
 }
 inline int group_grad_rows(int b, int c, int n) { return grad_rows(n, b, c); }
 inline int interp_grad_rows(int b, int c, int m) { return m > 0 ? grad_rows(m, b, c) : 0; }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 // launch KERNEL<..., CM> for the process-wide contraction mode
 #define U3D_PO_LAUNCH_CM(KERNEL, ...)                                                                 \

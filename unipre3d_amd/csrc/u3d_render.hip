@@ -1095,31 +1095,61 @@ static inline TileGrid tile_grid(const u3d_raster_desc& d, int tiles_x, int T) {
   return TileGrid{dim3((uint32_t)T, gy, gz), magic};
 }
 
+// host frame of one tile launch, built once from (d, b): what the three launchers and their reductions all pass on
+struct TileFrame {
+  int tiles_x, T, NV;
+  uint32_t ntiles;       // NV * T; nothing is launched when 0 (tg is then unset)
+  size_t NG;             // (view, Gaussian) pairs
+  TileGrid tg;
+  const uint2* rect;     // rects by Gaussian (through sorted_id) when rect_indirect, else the sorted copy
+  int rect_indirect;
+  uint32_t* tw;          // touched words (scene level only)
+  TileFrame(const u3d_raster_desc& d, const U3DBuffers& b) {
+    tiles_x = (d.image_width + U3D_TILE - 1) / U3D_TILE;
+    T = tiles_x * ((d.image_height + U3D_TILE - 1) / U3D_TILE);
+    NV = d.n_items * d.views_per_item;
+    ntiles = (uint32_t)(NV * T);
+    NG = (size_t)d.views_per_item * u3d_total_P(d);
+    tg = ntiles ? tile_grid(d, tiles_x, T) : TileGrid{};
+    rect_indirect = u3d_rect_indirect(d);
+    rect = rect_indirect ? b.rect : b.sorted_rect;
+    tw = u3d_uses_touched_words(d) ? b.touched_words : nullptr;
+  }
+};
+
+// The gradient reduction behind a tile launch: `rows` grid rows per view (the nsplit slices, then the loss row and the zero-fill rows
+// of the fused step); `tail` = what bwd_reduce_kernel takes beyond bwd_reduce1_kernel's list.
+template <typename Kernel, typename... Tail>
+static void launch_reduce(Kernel kern, const u3d_raster_desc& d, const U3DBuffers& b, const TileFrame& tf, int NK, int nsplit, int rows,
+                          double* acc, const float* part, int n_loss, const U3DLoss& loss, float* loss_out, hipStream_t s, Tail... tail) {
+  hipLaunchKernelGGL(kern, dim3(tf.NV, rows), dim3(REDUCE_THREADS), 0, s, u3d_span(d), tf.T, NK, nsplit, tf.NG, 0.5f * (float)d.image_width,
+                     0.5f * (float)d.image_height, b.sorted_id, b.conic_op, part,
+                     reinterpret_cast<const uint32_t*>(part + (size_t)tf.ntiles * BWD_PART_STRIDE), acc, b.clamped, tf.tw, n_loss,
+                     n_loss ? loss.partial : nullptr, n_loss ? loss.inv_count : 0.f, loss_out, tail...);
+}
+
 void u3d_launch_render_fwd(const u3d_raster_desc& d, const U3DBuffers& b, const float* bg, float* out_color,
                            float* out_invdepth, const U3DLoss& loss, hipStream_t s) {
-  const int tiles_x = (d.image_width + U3D_TILE - 1) / U3D_TILE, tiles_y = (d.image_height + U3D_TILE - 1) / U3D_TILE;
-  const int T = tiles_x * tiles_y;
-  const uint32_t ntiles = (uint32_t)(d.n_items * d.views_per_item * T);
-  if (ntiles == 0) return;
-  const TileGrid tg = tile_grid(d, tiles_x, T);
+  const TileFrame tf(d, b);
+  if (tf.ntiles == 0) return;
   auto* kern = out_invdepth ? render_fwd_wave_kernel<true> : render_fwd_wave_kernel<false>;
-  hipLaunchKernelGGL(kern, tg.grid, dim3(TILE_WAVES * U3D_WAVE), 0, s, u3d_span(d), d.image_height, d.image_width,
-                     tiles_x, T, ntiles, tg.magic, b.sorted_id, u3d_rect_indirect(d) ? b.rect : b.sorted_rect, u3d_rect_indirect(d), b.n_vis, b.xy, b.conic_op, b.rgbd, bg, out_color,
-                     out_invdepth, b.final_T, b.n_contrib, b.tile_last, loss);
+  hipLaunchKernelGGL(kern, tf.tg.grid, dim3(TILE_WAVES * U3D_WAVE), 0, s, u3d_span(d), d.image_height, d.image_width, tf.tiles_x, tf.T,
+                     tf.ntiles, tf.tg.magic, b.sorted_id, tf.rect, tf.rect_indirect, b.n_vis, b.xy, b.conic_op, b.rgbd, bg, out_color, out_invdepth,
+                     b.final_T, b.n_contrib, b.tile_last, loss);
 }
+
+// the instantiation for a call (pb = u3d_part_blocks; the pickers sit below the forward launcher so that the kernels are
+// instantiated, and so emitted, in the order the three launchers name them)
+static inline auto pick_fb(int pb) { return pb == 1 ? render_fb_wave_kernel<1> : render_fb_wave_kernel<U3D_PART_BLOCKS>; }
 
 void u3d_launch_render_fb(const u3d_raster_desc& d, const U3DBuffers& b, const float* bg, float* out_color,
                           const U3DLoss& loss, double* acc, float* part, float* loss_out, hipStream_t s,
                           float* zero_fill, size_t zero_floats, bool list_touched) {
-  const int tiles_x = (d.image_width + U3D_TILE - 1) / U3D_TILE, tiles_y = (d.image_height + U3D_TILE - 1) / U3D_TILE;
-  const int T = tiles_x * tiles_y;
-  const uint32_t ntiles = (uint32_t)(d.n_items * d.views_per_item * T);
-  const size_t NG = (size_t)d.views_per_item * u3d_total_P(d);
-  if (ntiles == 0 || NG == 0) return;
-  const TileGrid tg = tile_grid(d, tiles_x, T);
-  uint32_t* tw = u3d_uses_touched_words(d) ? b.touched_words : nullptr;
-  uint2* tl = (list_touched && tw) ? b.touched_list : nullptr;
-  uint32_t* tc = (list_touched && tw) ? b.touched_count : nullptr;
+  const TileFrame tf(d, b);
+  const uint32_t ntiles = tf.ntiles;
+  if (ntiles == 0 || tf.NG == 0) return;
+  uint2* tl = (list_touched && tf.tw) ? b.touched_list : nullptr;
+  uint32_t* tc = (list_touched && tf.tw) ? b.touched_count : nullptr;
 #ifdef U3D_TIMELINE
   {
     static int launches = 0;
@@ -1145,63 +1175,47 @@ void u3d_launch_render_fb(const u3d_raster_desc& d, const U3DBuffers& b, const f
     }
   }
 #endif
-  if (u3d_part_blocks(d) == 1)
-    hipLaunchKernelGGL(render_fb_wave_kernel<1>, tg.grid, dim3(TILE_WAVES * U3D_WAVE), 0, s, u3d_span(d), d.image_height, d.image_width,
-                       tiles_x, T, ntiles, tg.magic, NG, b.sorted_id, u3d_rect_indirect(d) ? b.rect : b.sorted_rect, u3d_rect_indirect(d), b.n_vis, b.xy, b.conic_op, b.rgbd, bg, out_color,
-                       acc, part, b.clamped, tw, tl, tc, loss);
-  else
-    hipLaunchKernelGGL(render_fb_wave_kernel<U3D_PART_BLOCKS>, tg.grid, dim3(TILE_WAVES * U3D_WAVE), 0, s, u3d_span(d), d.image_height,
-                       d.image_width, tiles_x, T, ntiles, tg.magic, NG, b.sorted_id, u3d_rect_indirect(d) ? b.rect : b.sorted_rect, u3d_rect_indirect(d), b.n_vis, b.xy, b.conic_op, b.rgbd, bg,
-                       out_color, acc, part, b.clamped, tw, tl, tc, loss);
-  const int nsplit = bwd_reduce_split(T, d.n_items * d.views_per_item);
-  const int NVi = d.n_items * d.views_per_item;
-  if (u3d_part_blocks(d) == 1) {
-    hipLaunchKernelGGL(bwd_reduce1_kernel, dim3(NVi, nsplit + 1), dim3(REDUCE_THREADS), 0, s,
-                       u3d_span(d), T, U3D_NACC - 1, nsplit, NG, 0.5f * (float)d.image_width, 0.5f * (float)d.image_height, b.sorted_id, b.conic_op, part,
-                       reinterpret_cast<const uint32_t*>(part + (size_t)ntiles * BWD_PART_STRIDE), acc, b.clamped, tw, (int)ntiles, loss.partial,
-                       loss.inv_count, loss_out);
+  const int pb = u3d_part_blocks(d);
+  auto* kern = pick_fb(pb);
+  hipLaunchKernelGGL(kern, tf.tg.grid, dim3(TILE_WAVES * U3D_WAVE), 0, s, u3d_span(d), d.image_height, d.image_width, tf.tiles_x, tf.T,
+                     ntiles, tf.tg.magic, tf.NG, b.sorted_id, tf.rect, tf.rect_indirect, b.n_vis, b.xy, b.conic_op, b.rgbd, bg, out_color, acc, part,
+                     b.clamped, tf.tw, tl, tc, loss);
+  const int nsplit = bwd_reduce_split(tf.T, tf.NV);
+  if (pb == 1) {
+    launch_reduce(bwd_reduce1_kernel, d, b, tf, U3D_NACC - 1, nsplit, nsplit + 1, acc, part, (int)ntiles, loss, loss_out, s);
   } else {
     // zero-fill rows (U3D_FLAG_SPARSE_BWD): ~256 extra workgroups of 640 threads, at most one per 64 KB to fill
     int zrows = 0;
     if (zero_fill && zero_floats > 0) {
       const size_t want = (zero_floats * sizeof(float) + 65535) / 65536;
-      zrows = (int)((want < 256 ? want : 256) + (size_t)NVi - 1) / NVi;
+      zrows = (int)((want < 256 ? want : 256) + (size_t)tf.NV - 1) / tf.NV;
       if (zrows < 1) zrows = 1;
     }
-    hipLaunchKernelGGL(bwd_reduce_kernel<U3D_PART_BLOCKS>, dim3(NVi, nsplit + 1 + zrows), dim3(REDUCE_THREADS), 0, s,
-                       u3d_span(d), T, U3D_NACC - 1, nsplit, NG, 0.5f * (float)d.image_width, 0.5f * (float)d.image_height, b.sorted_id, b.conic_op, part,
-                       reinterpret_cast<const uint32_t*>(part + (size_t)ntiles * BWD_PART_STRIDE), acc, b.clamped, tw, (int)ntiles, loss.partial,
-                       loss.inv_count, loss_out, tl, tc, zero_fill, zero_floats);
+    launch_reduce(bwd_reduce_kernel<U3D_PART_BLOCKS>, d, b, tf, U3D_NACC - 1, nsplit, nsplit + 1 + zrows, acc, part, (int)ntiles, loss,
+                  loss_out, s, tl, tc, zero_fill, zero_floats);
   }
+}
+
+static inline auto pick_bwd(bool invd, int pb) {
+  if (pb == 1) return invd ? render_bwd_wave_kernel<true, 1> : render_bwd_wave_kernel<false, 1>;
+  return invd ? render_bwd_wave_kernel<true, U3D_PART_BLOCKS> : render_bwd_wave_kernel<false, U3D_PART_BLOCKS>;
 }
 
 void u3d_launch_render_bwd(const u3d_raster_desc& d, const U3DBuffers& b, const float* bg, const float* dL_dcolor,
                            const float* dL_dinvdepth, const float* out_color, const U3DLoss& loss, double* acc,
                            float* part, hipStream_t s) {
-  const int tiles_x = (d.image_width + U3D_TILE - 1) / U3D_TILE, tiles_y = (d.image_height + U3D_TILE - 1) / U3D_TILE;
-  const int T = tiles_x * tiles_y;
-  const uint32_t ntiles = (uint32_t)(d.n_items * d.views_per_item * T);
-  const size_t NG = (size_t)d.views_per_item * u3d_total_P(d);
-  if (ntiles == 0 || NG == 0) return;
-  const TileGrid tg = tile_grid(d, tiles_x, T);
+  const TileFrame tf(d, b);
+  if (tf.ntiles == 0 || tf.NG == 0) return;
   const bool invd = dL_dinvdepth && loss.kind == 0;
-  uint32_t* tw = u3d_uses_touched_words(d) ? b.touched_words : nullptr;
-#define LAUNCH(INVD, PBV)                                                                                                   \
-  hipLaunchKernelGGL((render_bwd_wave_kernel<INVD, PBV>), tg.grid, dim3(TILE_WAVES * U3D_WAVE), 0, s, u3d_span(d), d.image_height, \
-                     d.image_width, tiles_x, T, ntiles, tg.magic, NG, b.sorted_id, u3d_rect_indirect(d) ? b.rect : b.sorted_rect, u3d_rect_indirect(d), b.xy, b.conic_op, b.rgbd, bg,    \
-                     dL_dcolor, dL_dinvdepth, b.final_T, b.n_contrib, b.tile_last, acc, part, out_color, b.clamped, tw, loss)
-  if (u3d_part_blocks(d) == 1) { if (invd) LAUNCH(true, 1); else LAUNCH(false, 1); }
-  else { if (invd) LAUNCH(true, U3D_PART_BLOCKS); else LAUNCH(false, U3D_PART_BLOCKS); }
-#undef LAUNCH
-  const int nsplit = bwd_reduce_split(T, d.n_items * d.views_per_item);
-  if (u3d_part_blocks(d) == 1)
-    hipLaunchKernelGGL(bwd_reduce1_kernel, dim3(d.n_items * d.views_per_item, nsplit), dim3(REDUCE_THREADS), 0, s,
-                       u3d_span(d), T, invd ? U3D_NACC : U3D_NACC - 1, nsplit, NG, 0.5f * (float)d.image_width, 0.5f * (float)d.image_height, b.sorted_id,
-                       b.conic_op, part, reinterpret_cast<const uint32_t*>(part + (size_t)ntiles * BWD_PART_STRIDE), acc, b.clamped, tw, 0, nullptr, 0.f,
-                       nullptr);
+  const int pb = u3d_part_blocks(d);
+  auto* kern = pick_bwd(invd, pb);
+  hipLaunchKernelGGL(kern, tf.tg.grid, dim3(TILE_WAVES * U3D_WAVE), 0, s, u3d_span(d), d.image_height, d.image_width, tf.tiles_x,
+                     tf.T, tf.ntiles, tf.tg.magic, tf.NG, b.sorted_id, tf.rect, tf.rect_indirect, b.xy, b.conic_op, b.rgbd, bg, dL_dcolor, dL_dinvdepth,
+                     b.final_T, b.n_contrib, b.tile_last, acc, part, out_color, b.clamped, tf.tw, loss);
+  const int nsplit = bwd_reduce_split(tf.T, tf.NV), NK = invd ? U3D_NACC : U3D_NACC - 1;
+  if (pb == 1)
+    launch_reduce(bwd_reduce1_kernel, d, b, tf, NK, nsplit, nsplit, acc, part, 0, loss, nullptr, s);
   else
-    hipLaunchKernelGGL(bwd_reduce_kernel<U3D_PART_BLOCKS>, dim3(d.n_items * d.views_per_item, nsplit), dim3(REDUCE_THREADS), 0, s,
-                       u3d_span(d), T, invd ? U3D_NACC : U3D_NACC - 1, nsplit, NG, 0.5f * (float)d.image_width, 0.5f * (float)d.image_height, b.sorted_id,
-                       b.conic_op, part, reinterpret_cast<const uint32_t*>(part + (size_t)ntiles * BWD_PART_STRIDE), acc, b.clamped, tw, 0, nullptr, 0.f,
-                       nullptr, (uint2*)nullptr, (uint32_t*)nullptr, (float*)nullptr, (size_t)0);
+    launch_reduce(bwd_reduce_kernel<U3D_PART_BLOCKS>, d, b, tf, NK, nsplit, nsplit, acc, part, 0, loss, nullptr, s, (uint2*)nullptr,
+                  (uint32_t*)nullptr, (float*)nullptr, (size_t)0);
 }

@@ -17,8 +17,11 @@
 #include <stdint.h>
 
 #include "unipre3d_selective_scan.h"
+#include "u3d_util.h"
 
 namespace {
+
+using namespace u3d_util;
 
 constexpr int NT = 256;                   // threads per workgroup (four waves)
 constexpr int NW = NT / 64;
@@ -27,14 +30,6 @@ constexpr int SLAB = U3D_SSCAN_SLAB;      // channels one backward workgroup wal
 constexpr int CPW = SLAB / NW;            // ... per wave
 constexpr int NPAR = NS + 2;              // per-(b,d) partials: dA[16], dD, ddelta_bias
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
-inline int steps_per_lane(int L) { return L <= 64 ? 1 : L <= 128 ? 2 : L <= 192 ? 3 : 4; }
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f(float old, float v) {   // lanes without a source (or outside ROW_MASK) keep `old`
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
 // (a, b) of this lane := (a, b) of the DPP source lane, THEN this lane's own; lanes without a source compose with the identity
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ void compose_from(float& a, float& b) {
@@ -50,18 +45,7 @@ __device__ __forceinline__ void wave_scan(float& a, float& b) {   // inclusive s
   compose_from<0x142, 0xa>(a, b);   // row_bcast:15 into rows 1 and 3
   compose_from<0x143, 0xc>(a, b);   // row_bcast:31 into rows 2 and 3
 }
-__device__ __forceinline__ float lane63(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); }
-__device__ __forceinline__ float wave_sum(float v) {              // the sum of the 64 lanes, in one fixed order, in every lane
-  v += dpp_f<0x111, 0xf>(0.f, v);
-  v += dpp_f<0x112, 0xf>(0.f, v);
-  v += dpp_f<0x114, 0xf>(0.f, v);
-  v += dpp_f<0x118, 0xf>(0.f, v);
-  v += dpp_f<0x142, 0xa>(0.f, v);
-  v += dpp_f<0x143, 0xc>(0.f, v);
-  return lane63(v);
-}
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
 struct Args {
   const float *u, *delta, *A, *Bm, *Cm, *Dv, *z, *delta_bias, *dout, *xsave_in;
@@ -116,7 +100,7 @@ __global__ __launch_bounds__(NT) void sscan_fwd_kernel(const Args p) {
         x = fmaf(ar[r], x, br[r]);
         y[r] = fmaf(cr[r], x, y[r]);
       }
-      carry[n] = fmaf(lane63(a), carry[n], lane63(bb));
+      carry[n] = fmaf(lane_f<63>(a), carry[n], lane_f<63>(bb));
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -225,7 +209,7 @@ __global__ __launch_bounds__(NT) void sscan_bwd_kernel(const Args p) {
         rb = __shfl(rb, 63 - lane);
         wave_scan(ra, rb);
         float h = fmaf(dpp_f<0x138, 0xf>(1.f, ra), hin, dpp_f<0x138, 0xf>(0.f, rb));
-        const float hout = fmaf(lane63(ra), hin, lane63(rb));
+        const float hout = fmaf(lane_f<63>(ra), hin, lane_f<63>(rb));
         h = __shfl(h, 63 - lane);
         float dAp = 0.f;
 #pragma unroll

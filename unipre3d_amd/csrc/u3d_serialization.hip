@@ -6,8 +6,11 @@
 #include <stdint.h>
 
 #include "unipre3d_serialization.h"
+#include "u3d_util.h"
 
 namespace {
+
+using namespace u3d_util;
 
 typedef unsigned long long u64;
 
@@ -18,9 +21,6 @@ constexpr int TILE = NT * ITEMS;
 constexpr int SCAN_NT = 1024;        // the one-workgroup exclusive scan
 
 inline int n_tiles(int n) { return (n + TILE - 1) / TILE; }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline int blocks(long long n, int per) { return (int)((n + per - 1) / per); }
-inline int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
 
 struct Scratch {   // carved out of the caller's buffer for K rows of n elements
   u64* keys[2];
@@ -45,8 +45,6 @@ size_t carve(void* base, int K, int n_rows, Scratch* s) {
   if (s) *s = t;
   return off;
 }
-
-__device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
 
 // ---- codes -----------------------------------------------------------------------------------------------------------------------
 // bit i of v (i < 21) to bit 3 i
@@ -116,23 +114,6 @@ __global__ __launch_bounds__(NT) void radix_hist_kernel(int shift, int pre, int 
   hist[(size_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];
 }
 
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* wt, uint32_t& all) {   // NT threads, wt: NW words of LDS
-  const uint32_t lane = lane_id();
-  const int wave = threadIdx.x >> 6;
-  uint32_t inc = x;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = (uint32_t)__shfl_up((int)inc, o);
-    if ((int)lane >= o) inc += u;
-  }
-  if (lane == 63) wt[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0;
-  all = 0;
-  for (int w = 0; w < NW; ++w) { if (w < wave) before += wt[w]; all += wt[w]; }
-  __syncthreads();
-  return before + inc - x;
-}
-
 __global__ __launch_bounds__(NT) void digit_scan_kernel(int nb, uint32_t* __restrict__ hist) {   // grid (256 digits, K rows)
   __shared__ uint32_t wt[NW];
   hist += (size_t)blockIdx.y * (nb + 1) * 256;
@@ -142,7 +123,7 @@ __global__ __launch_bounds__(NT) void digit_scan_kernel(int nb, uint32_t* __rest
     const int b = b0 + threadIdx.x;
     const uint32_t x = b < nb ? line[b] : 0u;
     uint32_t all;
-    const uint32_t e = block_excl_scan(x, wt, all);
+    const uint32_t e = block_excl_scan<NW>(x, wt, all);
     if (b < nb) line[b] = carry + e;
     carry += all;
   }
@@ -166,7 +147,7 @@ __global__ __launch_bounds__(NT) void radix_scatter_kernel(int shift, int pre, i
   const int tid = threadIdx.x, wave = tid >> 6;
   const uint32_t lane = lane_id();
   uint32_t all;
-  digit_base[tid] = block_excl_scan(hist[(size_t)nb * 256 + tid], wt, all) + hist[(size_t)tid * nb + blockIdx.x];
+  digit_base[tid] = block_excl_scan<NW>(hist[(size_t)nb * 256 + tid], wt, all) + hist[(size_t)tid * nb + blockIdx.x];
   for (int r = 0; r < ITEMS; ++r) {
     for (int w = 0; w < NW; ++w) wave_cnt[w][tid] = 0;
     __syncthreads();

@@ -7,8 +7,11 @@
 #include <algorithm>
 
 #include "unipre3d_sparseconv.h"
+#include "u3d_util.h"
 
 namespace {
+
+using namespace u3d_util;
 
 constexpr int NT = 256;              // threads per workgroup (four waves)
 constexpr int NW = NT / 64;
@@ -21,9 +24,6 @@ constexpr int SMALL_C = 8;           // a channel count at or below this takes t
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 inline int n_tiles(int n) { return (n + TILE - 1) / TILE; }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-__host__ __device__ inline int blocks(long long n, int per) { return (int)((n + per - 1) / per); }
-inline int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
 inline int bit_len(unsigned long long v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
 
 struct Scratch {   // carved out of the caller's buffer; every array sized for n rows
@@ -51,8 +51,6 @@ size_t carve(void* base, int n_rows, Scratch* s) {
   if (s) *s = t;
   return off;
 }
-
-__device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
 
 // first position of key k in the ascending keys[0, n)
 __device__ __forceinline__ int lower_bound(const unsigned long long* __restrict__ keys, int n, unsigned long long k) {
@@ -88,23 +86,6 @@ __global__ __launch_bounds__(NT) void radix_hist_kernel(Digit dg, int n, int nb,
   hist[(size_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];   // digit-major: a scan of each digit's row gives (digit, tile) bases
 }
 
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* wt, uint32_t& all) {   // NT threads, wt: NW words of LDS
-  const uint32_t lane = lane_id();
-  const int wave = threadIdx.x >> 6;
-  uint32_t inc = x;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = (uint32_t)__shfl_up((int)inc, o);
-    if ((int)lane >= o) inc += u;
-  }
-  if (lane == 63) wt[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0;
-  all = 0;
-  for (int w = 0; w < NW; ++w) { if (w < wave) before += wt[w]; all += wt[w]; }
-  __syncthreads();
-  return before + inc - x;
-}
-
 __global__ __launch_bounds__(NT) void row_scan_kernel(int nb, uint32_t* __restrict__ hist, uint32_t* __restrict__ tot) {
   __shared__ uint32_t wt[NW];
   uint32_t* row = hist + (size_t)blockIdx.x * nb;
@@ -113,7 +94,7 @@ __global__ __launch_bounds__(NT) void row_scan_kernel(int nb, uint32_t* __restri
     const int b = b0 + threadIdx.x;
     const uint32_t x = b < nb ? row[b] : 0u;
     uint32_t all;
-    const uint32_t e = block_excl_scan(x, wt, all);
+    const uint32_t e = block_excl_scan<NW>(x, wt, all);
     if (b < nb) row[b] = carry + e;
     carry += all;
   }
@@ -132,7 +113,7 @@ __global__ __launch_bounds__(NT) void radix_scatter_kernel(Digit dg, int n, int 
   const int tid = threadIdx.x, wave = tid >> 6;
   const uint32_t lane = lane_id();
   uint32_t all;
-  digit_base[tid] = block_excl_scan(tot[tid], wt, all) + hist[(size_t)tid * nb + blockIdx.x];
+  digit_base[tid] = block_excl_scan<NW>(tot[tid], wt, all) + hist[(size_t)tid * nb + blockIdx.x];
   for (int r = 0; r < ITEMS; ++r) {
     for (int w = 0; w < NW; ++w) wave_cnt[w][tid] = 0;
     __syncthreads();

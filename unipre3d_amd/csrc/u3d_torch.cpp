@@ -17,6 +17,7 @@
 #include <tuple>
 #include <unordered_map>
 
+#include "u3d_util.h"
 #include "unipre3d_rasterizer.h"
 
 #ifndef U3D_BINDING_NO_SPARSE
@@ -27,6 +28,7 @@ constexpr int64_t kSparseMinP = U3D_SPARSE_BWD_MIN_P;   // the library honours U
 namespace {
 
 using torch::Tensor;
+using u3d_util::align256;
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
@@ -35,8 +37,6 @@ struct Plan {
   u3d_scratch_sizes s;
   size_t o_binning, o_image, fwd_scratch;   // offsets inside the forward arena (256-byte aligned)
 };
-
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // descriptors are small PODs: cache the scratch sizes per distinct descriptor (the per-view route reuses ONE shape all step long).
 // Returned BY VALUE and stored by value in the autograd node (`plan_save` / `plan_load`), so the cache can be bounded: ragged

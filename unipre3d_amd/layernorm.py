@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import check, on_device, stream_ptr
-from .causal_conv1d import load, scratch
+from .causal_conv1d import load
 
 EXPORTS = ("u3d_addnorm_max_n", "u3d_addnorm_bwd_waves", "u3d_addnorm_bwd_scratch_bytes", "u3d_addnorm_fwd", "u3d_addnorm_bwd")
 
@@ -63,7 +63,7 @@ class _AddNorm(torch.autograd.Function):
         dweight = torch.empty_like(weight)
         dbias = torch.empty_like(weight) if has_bias else None
         nbytes = int(lib.u3d_addnorm_bwd_scratch_bytes(M, N))
-        buf, base = scratch(nbytes, dev)
+        buf, base = _lib.scratch(nbytes, dev)
         p = _lib.ptr
         check(lib.u3d_addnorm_bwd(p(dy), p(dres), p(r), p(weight), p(mean), p(rstd), p(dx), p(dweight), p(dbias), base, nbytes, M, N,
                                   int(is_rms_norm), stream_ptr(dev)), "u3d_addnorm_bwd", named=False)

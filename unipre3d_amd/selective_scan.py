@@ -74,11 +74,10 @@ class _SelectiveScan(torch.autograd.Function):
         dz = torch.empty_like(z) if z is not None else None
         dbias = torch.empty_like(delta_bias) if delta_bias is not None else None
         nbytes = int(lib.u3d_sscan_bwd_scratch_bytes(Bsz, Dm, G, L))
-        scratch = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        base = (scratch.data_ptr() + 255) & ~255
+        buf, base = _lib.scratch(nbytes, dev)
         p = _lib.ptr
         check(lib.u3d_sscan_bwd(p(u), p(delta), p(A), p(B), p(C), p(D), p(z), p(delta_bias), p(dout), p(xsave), p(du), p(ddelta), p(dA),
-                                p(dB), p(dC), p(dD), p(dz), p(dbias), ctypes.c_void_p(base), nbytes, Bsz, Dm, G, D_STATE, L,
+                                p(dB), p(dC), p(dD), p(dz), p(dbias), base, nbytes, Bsz, Dm, G, D_STATE, L,
                                 int(ctx.delta_softplus), stream_ptr(dev)), "u3d_sscan_bwd", named=False)
         return du, ddelta, dA, dB, dC, dD, dz, dbias, None, None
 
