@@ -90,6 +90,18 @@ def test_conv_lengths_all_gradients(cc, L):
     _conv_case(cc, f"conv_len_L{L}", 2, 5, L)
 
 
+@pytest.mark.parametrize("batch", [1, 3])
+def test_conv_batch_reduction_of_dweight_and_dbias(cc, batch):
+    """dweight and dbias are summed over b from per-(b, d) partials: one row and three."""
+    _conv_case(cc, f"conv_batch_B{batch}_L129", batch, 5, 129)
+
+
+@pytest.mark.parametrize("dim", [1, 63, 64, 65, 130])
+def test_conv_channel_counts(cc, dim):
+    """One (b, d) row per wave, four waves a workgroup: a single channel, and row counts around one and two reduce workgroups."""
+    _conv_case(cc, f"conv_D{dim}_L65", 2, dim, 65, 4)
+
+
 def test_conv_lengths_around_the_chunk(cc):
     """The chunk a wave covers before it moves on (and carries the halo in registers), from the library: one below, at, one above, and
     one step into a third chunk."""

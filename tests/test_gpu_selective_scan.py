@@ -87,6 +87,21 @@ def test_channels_and_groups(ss, dim, groups, L):
     _device_case(ss, f"ch_D{dim}_G{groups}_L{L}", 2, dim, L, groups=groups)
 
 
+@pytest.mark.parametrize("dim,groups,L", [(1, 1, 65), (3, 1, 65), (4, 1, 65), (17, 1, 65), (63, 1, 65), (64, 1, 65), (65, 1, 65), (129, 1, 65),
+                                          (130, 2, 65), (192, 3, 65), (129, 1, 257)])
+def test_backward_channel_classes(ss, dim, groups, L):
+    """A backward workgroup is four waves on a slab of 64 channels of one group, 16 channels a wave: one wave alone (D = 1), a wave short
+    of four (3), exactly four (4), one past a wave's 16 (17), one short of a slab (63), a full slab (64), slab + 1 (65), three slabs (129),
+    two groups of two slabs with a one-channel tail each (130, 2), three groups of one slab (192, 3); and three slabs over two passes."""
+    _device_case(ss, f"cls_D{dim}_G{groups}_L{L}", 2, dim, L, groups=groups)
+
+
+@pytest.mark.parametrize("batch", [1, 3])
+def test_batch_reduction_of_the_parameter_gradients(ss, batch):
+    """dA, dD and ddelta_bias are summed over b from per-(b, d) partials, dB / dC come from (B, nslab, N, L) partials: one row and three."""
+    _device_case(ss, f"batch_B{batch}_D70_G1_L129", batch, 70, 129, groups=1)
+
+
 @pytest.mark.parametrize("softplus", [False, True])
 @pytest.mark.parametrize("has_bias", [False, True])
 @pytest.mark.parametrize("has_z", [False, True])
@@ -180,8 +195,9 @@ def test_impulse_decay(ss, L, k):
 
 
 def test_two_runs_are_bit_identical(ss):
-    """Multi-pass, multi-slab (the partials + reduce path) and the single-slab direct path: out and every gradient, twice."""
-    for dim, groups, L in ((70, 1, 257), (70, 2, 129)):
+    """Multi-pass, multi-slab (the partials + reduce path), the single-slab direct path and three slabs over two passes: out and every
+    gradient, twice."""
+    for dim, groups, L in ((70, 1, 257), (70, 2, 129), (129, 1, 257)):
         t, dout, *_ = _reference(2, dim, L, groups, True, True, True, True)
         td = R.cast(t, torch.float32, DEV)
         a = R.run_with_grads(ss.selective_scan_fn, td, dout.float().to(DEV), delta_softplus=True)
