@@ -17,6 +17,8 @@
  * zbuf: u3d_zbuffer_fusion_zbuf_bytes(B, H, W) bytes (B*H*W uint64 winner words), written by the forward and READ by the backward
  *       (keep it with sel); N < 2^32.
  * grad_features need NOT be initialised (ABI 2; ABI 1 accumulated with float atomics into a caller-zeroed buffer).
+ * Alignment: when H*W is a multiple of 4 the backward reads zbuf and writes grad_features with 16-byte accesses, so both pointers must
+ *       be 16-byte aligned there; the backward returns 1 otherwise, before any launch.  Every other pointer needs its element's alignment.
  * Returns 0 ok, 1 invalid argument, 2 unsupported shape, 3 launch failure.
  */
 #ifndef UNIPRE3D_FUSION_H

@@ -153,6 +153,9 @@ int u3d_zbuffer_fusion_backward(int B, int N, int C, int H, int W, const float* 
   }
   if (!grad_mapped || !sel || !zbuf) return 1;
   if (B > 65535 || C > 65535) return 2;
+  // grad_plane_kernel reads two winner words and stores four floats per access: both bases must be 16-byte aligned (every plane is HW*4 bytes
+  // and every item HW*8 bytes behind them, multiples of 16 when HW % 4 == 0)
+  if ((HW & 3) == 0 && (((uintptr_t)zbuf | (uintptr_t)grad_features) & 15) != 0) return 1;
   const unsigned long long* z = (const unsigned long long*)zbuf;
   if ((HW & 3) == 0) {
     hipLaunchKernelGGL(grad_plane_kernel, dim3(C, B), dim3(256), 0, s, N, C, HW, grad_mapped, z, grad_features);
