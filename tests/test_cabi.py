@@ -166,6 +166,13 @@ def test_product_path_refuses_cpu_tensors():
         r(means3D=torch.zeros(4, 3), means2D=torch.zeros(4, 3), opacities=torch.ones(4, 1), colors_precomp=torch.ones(4, 3))
 
 
+def test_binding_exports_exactly_its_nine_functions():
+    from unipre3d_amd import rasterizer
+    names = {n for n in dir(rasterizer._C()) if not n.startswith("_")}
+    assert names == {"rasterize_view", "rasterize_batched", "render_view", "viewspace_sink", "render_loss_step", "unit_tensor",
+                     "abi_version", "clear_workspaces", "workspaces"}
+
+
 def test_product_never_imports_oracle():
     for dirpath, _, files in os.walk(os.path.join(ROOT, "unipre3d_amd")):
         for f in files:

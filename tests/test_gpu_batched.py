@@ -429,7 +429,18 @@ def test_operator_backward_reuses_its_workspace_with_clean_accumulators(level, P
     assert C.workspaces()[:3] == (1, 1, 0)
 
 
-def test_fused_step_backward_half_scales_by_grad_output_and_survives_interleaving():
+# the fused step's lease scenarios at both levels: object (every sum in a fixed order: bit-identical) and the smallest scene-level set
+# above U3D_SPARSE_BWD_MIN_P = 4096 (U3D_FLAG_SPARSE_BWD on: d(head_out) pre-allocated in forward, consumed by one backward,
+# re-created on a recompute; sums through f64 atomics: rel-L2 < 1e-6 where the object case asserts bit equality)
+_STEP_LEVELS = {"object": (128, "focal_l2"), "scene": (4097, "l2")}
+
+
+def _same_gradient(level, a, b):
+    return torch.equal(a, b) if level == "object" else rel_l2(a.cpu().numpy(), b.cpu().numpy()) < 1e-6
+
+
+@pytest.mark.parametrize("level", ["object", "scene"])
+def test_fused_step_backward_half_scales_by_grad_output_and_survives_interleaving(level):
     """ABI 4: the autograd forward runs projection -> tiles -> reduce, the autograd backward runs the chain rule and multiplies by
     autograd's grad_output INSIDE the projection-backward kernel (no d_head * g launch).  Checks: (a) loss.backward(),
     backward_unit(loss) and (3 * loss).backward() / 3 agree (bit-identical for the first two: g = 1 is an exact multiply);
@@ -438,13 +449,15 @@ def test_fused_step_backward_half_scales_by_grad_output_and_survives_interleavin
     second backward works (the forward half is recomputed); (e) one scratch buffer per stream is all that is ever cached."""
     from unipre3d_amd import fused, rasterizer
     C = rasterizer._C()
-    _, b1 = _batch(2, 128, 2, 64, 64, level="object", seed=31)
-    _, b2 = _batch(2, 128, 2, 64, 64, level="object", seed=32)
+    P, loss_kind = _STEP_LEVELS[level]
+    same = lambda a, b: _same_gradient(level, a, b)
+    _, b1 = _batch(2, P, 2, 64, 64, level=level, seed=31)
+    _, b2 = _batch(2, P, 2, 64, 64, level=level, seed=32)
 
     def fwd(bd):
         h = bd.raw.permute(0, 2, 1).contiguous().requires_grad_(True)
         loss, _, _ = fused.render_loss_fused(h, bd.center, bd.world_view, bd.full_proj, bd.camera_center, bd.gt, bd.bg, bd.fov_deg, 64, 64,
-                                             level="object", offset_scale=bd.offset_scale, loss_kind="focal_l2", return_images=False)
+                                             level=level, offset_scale=bd.offset_scale, loss_kind=loss_kind, return_images=False)
         return h, loss
 
     C.clear_workspaces()
@@ -452,7 +465,7 @@ def test_fused_step_backward_half_scales_by_grad_output_and_survives_interleavin
     h, l = fwd(b1); fused.backward_unit(l); g_unit = h.grad.clone()
     h, l = fwd(b1); (3.0 * l).backward(); g_3 = h.grad.clone() / 3.0
     h, l = fwd(b2); l.backward(); g2_ref = h.grad.clone()
-    assert torch.equal(g_plain, g_unit)
+    assert same(g_plain, g_unit)
     assert rel_l2(g_3.cpu().numpy(), g_plain.cpu().numpy()) < 1e-6
     assert C.workspaces()[:3] == (1, 1, 0)
     # (b) interleaved
@@ -460,19 +473,19 @@ def test_fused_step_backward_half_scales_by_grad_output_and_survives_interleavin
     hb, lb = fwd(b2)
     assert C.workspaces()[2] == 1                       # the cached buffer is leased to the second forward; the first keeps its own
     la.backward(); lb.backward()
-    assert torch.equal(ha.grad, g_plain) and torch.equal(hb.grad, g2_ref)
+    assert same(ha.grad, g_plain) and same(hb.grad, g2_ref)
     assert C.workspaces()[:3] == (1, 1, 0)
     # (c) dropped loss
     hd, ld = fwd(b1)
     del hd, ld
     h, l = fwd(b2); l.backward()
-    assert torch.equal(h.grad, g2_ref)
+    assert same(h.grad, g2_ref)
     h, l = fwd(b1); l.backward()
-    assert torch.equal(h.grad, g_plain)
+    assert same(h.grad, g_plain)
     # (d) second backward
     h, l = fwd(b1)
     l.backward(retain_graph=True)
-    assert torch.equal(h.grad, g_plain)
+    assert same(h.grad, g_plain)
     h.grad = None
     (2.0 * l).backward()
     assert rel_l2(h.grad.cpu().numpy() / 2.0, g_plain.cpu().numpy()) < 1e-6
@@ -500,7 +513,8 @@ def test_ragged_steps_share_one_scratch_and_never_accumulate():
         loss.backward()
         return loss.detach().clone(), hp.grad.clone()
 
-    shapes = [([300, 500], 1), ([700, 100, 250], 2), ([300, 500], 3), ([64, 65], 4), ([300, 500], 3)]
+    # ([4097, 130]: ragged AND above U3D_SPARSE_BWD_MIN_P -- the pre-allocated d(head_out) starts from zeros)
+    shapes = [([300, 500], 1), ([700, 100, 250], 2), ([300, 500], 3), ([64, 65], 4), ([300, 500], 3), ([4097, 130], 5)]
     fresh = []
     for sizes, seed in shapes:
         C.clear_workspaces()
@@ -821,28 +835,59 @@ class _DropGrad(torch.autograd.Function):
         return None
 
 
-def test_fused_step_backward_after_an_unused_loss_recomputes():
+@pytest.mark.parametrize("level", ["object", "scene"])
+def test_fused_step_backward_after_an_unused_loss_recomputes(level):
     """A retained node whose first backward arrived with an UNDEFINED gradient for the loss released its lease on the backward
     scratch; a later backward through the same node must recompute the forward half instead of reading a buffer that another
     forward has reused in the meantime."""
     from unipre3d_amd import fused
-    _, b = _batch(2, 128, 2, 64, 64, level="object", seed=17)
+    P, loss_kind = _STEP_LEVELS[level]
+    kw = dict(level=level, loss_kind=loss_kind, return_images=False)
+    _, b = _batch(2, P, 2, 64, 64, level=level, seed=17)
     h = b.raw.permute(0, 2, 1).contiguous().requires_grad_(True)
     args = (b.center, b.world_view, b.full_proj, b.camera_center, b.gt, b.bg, b.fov_deg, 64, 64)
-    ref_loss, _, _ = fused.render_loss_fused(h, *args, level="object", return_images=False)
+    ref_loss, _, _ = fused.render_loss_fused(h, *args, **kw)
     ref_loss.backward()
     g_ref = h.grad.clone(); h.grad = None
-    loss, _, _ = fused.render_loss_fused(h, *args, level="object", return_images=False)
+    loss, _, _ = fused.render_loss_fused(h, *args, **kw)
     _DropGrad.apply(loss).backward(retain_graph=True)                  # the step's node sees an undefined gradient
     assert h.grad is None or not bool(h.grad.any())
     h.grad = None
     h2 = (h.detach() * 0.5).requires_grad_(True)                         # another forward takes over the released scratch ...
-    l2, _, _ = fused.render_loss_fused(h2, *args, level="object", return_images=False)
+    l2, _, _ = fused.render_loss_fused(h2, *args, **kw)
     loss.backward()                                                     # ... before the retained node is backpropagated for real
     l2.backward()
     torch.cuda.synchronize()
     assert rel_l2(h.grad.cpu().numpy(), g_ref.cpu().numpy()) < 1e-6
     assert bool(torch.isfinite(h2.grad).all()) and bool(h2.grad.any())
+
+
+def test_refused_step_leaves_no_lease_and_no_promise():
+    """A step the library refuses in its argument check -- after the binding has taken the backward scratch's lease, before anything
+    is launched -- must hand the lease back WITHOUT the accumulators-are-zero promise (nothing vouches for them), and the next good
+    step must equal one that never met the failure."""
+    from unipre3d_amd import fused, rasterizer
+    C = rasterizer._C()
+    _, b = _batch(2, 128, 2, 64, 64, level="object", seed=23)
+    args = (b.center, b.world_view, b.full_proj, b.camera_center, b.gt, b.bg, b.fov_deg, 64, 64)
+
+    def good():
+        h = b.raw.permute(0, 2, 1).contiguous().requires_grad_(True)
+        loss, _, _ = fused.render_loss_fused(h, *args, level="object", offset_scale=b.offset_scale, loss_kind="focal_l2", return_images=False)
+        loss.backward()
+        return loss.detach().clone(), h.grad.clone()
+
+    C.clear_workspaces()
+    l0, g0 = good()
+    assert C.workspaces()[:3] == (1, 1, 0)
+    h = b.raw.permute(0, 2, 1).contiguous().requires_grad_(True)
+    with pytest.raises(RuntimeError, match="invalid argument"):
+        fused.render_loss_fused(h, *args, level="object", offset_scale=b.offset_scale, loss_kind="focal_l2", non_bg_color_loss_rate=0.0,
+                                bg_color_loss_rate=0.0, return_images=False)
+    assert C.workspaces()[:3] == (1, 0, 0)              # the lease is back, the promise is gone
+    l1, g1 = good()
+    assert torch.equal(l1, l0) and torch.equal(g1, g0)
+    assert C.workspaces()[:3] == (1, 1, 0)
 
 
 def test_fused_step_is_capturable_in_a_hip_graph():

@@ -1,6 +1,11 @@
-// torch binding of the drop-in operator: `_C.rasterize_gaussians` as a C++ autograd function over the C-ABI of
-// libunipre3d_rasterizer.so (include/unipre3d_rasterizer.h).  It is what the third-party package's own `_C` extension is to
-// its Python wrapper: the reference calls the operator once per object and view
+// torch binding of the drop-in operator: C++ autograd functions over the C-ABI of libunipre3d_rasterizer.so
+// (include/unipre3d_rasterizer.h).  The module exports
+//   rasterize_view / rasterize_batched   the operator: one view with the reference's own tensor shapes / sets x views in one call
+//   render_view / viewspace_sink         the per-view wrapper's whole body as one call, and its gradient-sink leaf
+//   render_loss_step / unit_tensor       the fused training step in autograd's two halves, and the cached dL/dloss = 1
+//   abi_version, workspaces, clear_workspaces
+// It is what the third-party package's own `_C` extension is to its Python wrapper: the reference calls the
+// operator once per object and view
 // (train_network.py:418-446 -> gaussian_renderer/__init__.py:89-97), 128 forward + 128 backward calls per C2 step, so the
 // per-call host cost IS the cost of that route.  This file holds no arithmetic: it validates, allocates outputs / scratch
 // with torch's caching allocator, takes torch's current HIP stream and calls the extern "C" entry points.
@@ -10,7 +15,6 @@
 
 #include <c10/hip/HIPStream.h>
 
-#include <array>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -31,6 +35,7 @@ using torch::Tensor;
 using u3d_util::align256;
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
+using OptTensor = c10::optional<Tensor>;
 
 struct Plan {
   u3d_raster_desc d;
@@ -39,7 +44,7 @@ struct Plan {
 };
 
 // descriptors are small PODs: cache the scratch sizes per distinct descriptor (the per-view route reuses ONE shape all step long).
-// Returned BY VALUE and stored by value in the autograd node (`plan_save` / `plan_load`), so the cache can be bounded: ragged
+// Returned BY VALUE and stored by value in the autograd node (`record_save` / `record_load`), so the cache can be bounded: ragged
 // scene-level batches bring a new total_P almost every step.
 constexpr size_t kPlanCacheMax = 64;
 std::string desc_key(const u3d_raster_desc& d) {
@@ -65,12 +70,14 @@ Plan plan_for(const u3d_raster_desc& d) {
   cache->emplace(std::move(key), p);
   return p;
 }
-inline std::string plan_save(const Plan& p) { return std::string(reinterpret_cast<const char*>(&p), sizeof(Plan)); }
-inline Plan plan_load(const std::string& bytes) {
-  Plan p{};
-  TORCH_CHECK(bytes.size() == sizeof(Plan), "corrupt plan record");
-  std::memcpy(&p, bytes.data(), sizeof(Plan));
-  return p;
+// what a node keeps between forward and backward besides tensors: ONE POD (a Plan, the step's StepRecord) as a byte string
+template <typename T> inline std::string record_save(const T& r) { return std::string(reinterpret_cast<const char*>(&r), sizeof(T)); }
+template <typename T> inline T record_load(const c10::IValue& v) {
+  const std::string& bytes = v.toStringRef();
+  T r{};
+  TORCH_CHECK(bytes.size() == sizeof(T), "corrupt node record");
+  std::memcpy(&r, bytes.data(), sizeof(T));
+  return r;
 }
 
 // Backward scratch: ONE grow-only buffer per (device, stream).  A call that completes leaves its gradient accumulators zero, so
@@ -80,12 +87,13 @@ inline Plan plan_load(const std::string& bytes) {
 // The fused step holds its lease from the autograd forward to the autograd backward: a second forward in between (or a node
 // dropped without backward) finds the lease outstanding and takes a fresh buffer, so a pending backward never loses its data.
 struct Workspace { Tensor buf; std::string clean_key; bool outstanding = false; uint64_t ticket = 0; };
-struct Lease { Tensor buf; bool clean; uint64_t ticket; };
+struct Lease { Tensor buf; bool clean; uint64_t ticket; std::string shape_key; };
 using WsKey = std::pair<int, void*>;   // device, stream
 std::mutex g_ws_mu;
 auto* g_ws = new std::map<WsKey, Workspace>();   // (heap, never destroyed: HIP tensors must not be freed during static destruction)
 uint64_t g_ws_ticket = 0;
-Lease workspace_acquire(const WsKey& key, const Plan& plan, const std::string& shape_key, const at::TensorOptions& byte_opts) {
+Lease workspace_acquire(const WsKey& key, const Plan& plan, const at::TensorOptions& byte_opts) {
+  std::string shape_key = desc_key(plan.d);
   std::lock_guard<std::mutex> lock(g_ws_mu);
   Workspace& ws = (*g_ws)[key];
   const int64_t need = (int64_t)plan.s.backward_bytes;
@@ -97,7 +105,7 @@ Lease workspace_acquire(const WsKey& key, const Plan& plan, const std::string& s
   ws.clean_key.clear();          // the promise is withdrawn while a call is in flight on the host: a failed call leaves none behind
   ws.outstanding = true;
   ws.ticket = ++g_ws_ticket;
-  return {ws.buf, clean, ws.ticket};
+  return {ws.buf, clean, ws.ticket, std::move(shape_key)};
 }
 // the call (or, for the fused step, its backward half) succeeded: its accumulators are zero again.  zeroed = false: the lease
 // ends without that promise (the backward half was skipped).
@@ -108,6 +116,25 @@ void workspace_release(const WsKey& key, uint64_t ticket, const std::string& sha
   it->second.outstanding = false;
   if (zeroed) it->second.clean_key = shape_key;
 }
+// The lease protocol in one place.  Construction acquires; apply_clean() passes the buffer's promise on to the call's descriptor;
+// commit() ends the lease after a call that succeeded, leaving the promise for the next call of this shape; hold() hands the ticket
+// to a caller whose lease outlives the scope (the fused step's forward: ended by its backward half with workspace_release).  A scope
+// left in any other way -- a failed call, an exception -- ends the lease WITHOUT the promise: nothing vouches for the accumulators.
+struct ScopedLease : Lease {   // buf, clean, ticket
+  ScopedLease(const WsKey& key, const Plan& plan, const at::TensorOptions& byte_opts) : Lease(workspace_acquire(key, plan, byte_opts)), key_(key) {}
+  ScopedLease(const ScopedLease&) = delete;
+  ~ScopedLease() { if (armed_) workspace_release(key_, ticket, shape_key, false); }
+  void apply_clean(u3d_raster_desc& d) const { if (clean) d.flags |= U3D_FLAG_ACC_CLEAN; }
+  void commit() { armed_ = false; workspace_release(key_, ticket, shape_key, true); }
+  uint64_t hold() { armed_ = false; return ticket; }
+
+ private:
+  const WsKey key_;
+  bool armed_ = true;
+};
+
+// The one failure check of every C-ABI call (tests match the error string, e.g. "invalid argument").
+inline void check_rc(int rc, const char* what) { TORCH_CHECK(rc == U3D_OK, what, " failed: ", u3d_error_string(rc), " (code ", rc, ")"); }
 
 inline const float* fptr(const Tensor& t) { return (t.defined() && t.numel() > 0) ? t.data_ptr<float>() : nullptr; }
 inline float* fptr_mut(Tensor& t) { return (t.defined() && t.numel() > 0) ? t.data_ptr<float>() : nullptr; }
@@ -116,6 +143,11 @@ inline Tensor f32c(const Tensor& t, const c10::Device& dev) {
   if (!t.defined()) return t;
   if (t.device() == dev && t.scalar_type() == at::kFloat && t.is_contiguous()) return t;
   return t.to(dev, at::kFloat).contiguous();
+}
+// empty tensors count as absent (upstream's convention for colors_precomp / cov3D_precomp); present ones become contiguous fp32 on `dev`
+inline OptTensor opt(const OptTensor& t, const c10::Device& dev) {
+  if (t.has_value() && t->defined() && t->numel() > 0) return f32c(*t, dev);
+  return c10::nullopt;
 }
 
 inline void* current_stream(const c10::Device& dev) {
@@ -126,10 +158,49 @@ inline void* current_stream(const c10::Device& dev) {
   return (void*)c10::hip::getCurrentHIPStream().stream();
 }
 
+// a ragged batch's prefix sums, trusted by the kernels (checked on the device only with U3D_FLAG_DEBUG): what the host can see of them.
+// expected_numel: n_items + 1 where the caller states n_items itself (the operator); the fused step derives n_items from the table.
+inline void check_item_offsets(const Tensor& offsets, const c10::Device& dev, int64_t expected_numel = -1) {
+  TORCH_CHECK(offsets.device() == dev && offsets.scalar_type() == at::kInt && offsets.is_contiguous() &&
+                  (expected_numel < 0 || offsets.numel() == expected_numel),
+              "item_offsets must be a contiguous int32 tensor", expected_numel < 0 ? "" : " of n_items + 1 prefix sums", " on the Gaussians' device");
+}
+inline const int32_t* offsets_ptr(const Tensor& offsets) { return offsets.defined() ? offsets.data_ptr<int32_t>() : nullptr; }
+
+// The one place that fills u3d_raster_desc.  `offsets` undefined: a uniform batch (total_P 0).
+u3d_raster_desc make_desc(int64_t n_items, int64_t vpi, int64_t P, int64_t H, int64_t W, double tanfovx, double tanfovy, double scale_modifier,
+                          int64_t sh_degree, int64_t sh_coeffs, int64_t flags, int64_t total_P = 0, const Tensor& offsets = Tensor()) {
+  u3d_raster_desc d{};
+  d.n_items = (int32_t)n_items; d.views_per_item = (int32_t)vpi; d.P = (int32_t)P;
+  d.image_height = (int32_t)H; d.image_width = (int32_t)W;
+  d.tanfovx = (float)tanfovx; d.tanfovy = (float)tanfovy; d.scale_modifier = (float)scale_modifier;
+  d.sh_degree = (int32_t)sh_degree; d.sh_coeffs = (int32_t)sh_coeffs; d.flags = (int32_t)flags;
+  d.total_P = (int32_t)total_P;
+  d.item_offsets = offsets_ptr(offsets);
+  return d;
+}
+
+// The forward arena: one byte tensor carved geom | binning | tail at 256-byte aligned offsets, kept by the node for its backward.
+// tail = the image buffers (operator, per-view route) or the fused step's buffers, which take their place (no image buffer there).
+struct ForwardArena {
+  enum Tail { kImage, kFused };
+  ForwardArena(const Plan& plan, Tail tail, const at::TensorOptions& byte_opts)
+      : ForwardArena(plan, at::empty({(int64_t)(tail == kFused ? plan.o_image + align256(plan.s.fused_bytes) : plan.fwd_scratch)}, byte_opts)) {}
+  ForwardArena(const Plan& plan, const Tensor& saved) : buf(saved), o_binning(plan.o_binning), o_tail(plan.o_image) {}   // (backward)
+  void* geom() const { return buf.data_ptr(); }
+  void* binning() const { return (char*)buf.data_ptr() + o_binning; }
+  void* tail() const { return (char*)buf.data_ptr() + o_tail; }
+  const Tensor buf;
+  const size_t o_binning, o_tail;
+};
+
+struct OpRecord { Plan plan; bool single, has_means2D; };   // what the operator's node keeps besides tensors
+
 struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
   // (optional inputs travel as c10::optional: the C++ autograd function machinery records device / layout of every plain Tensor
   // argument and refuses undefined ones)
-  using OptTensor = c10::optional<Tensor>;
+  // save_for_backward's order
+  enum Saved { kMeans3D, kShs, kColors, kOpac, kScales, kRots, kCov, kView, kProj, kCampos, kBg, kRadii, kArena, kOffsets };
   static variable_list forward(AutogradContext* ctx, Tensor means3D, OptTensor means2D_, OptTensor shs_, OptTensor colors_, Tensor opac,
                                OptTensor scales_, OptTensor rots_, OptTensor cov_, Tensor view, Tensor proj, Tensor campos, Tensor bg,
                                int64_t n_items, int64_t vpi, int64_t H, int64_t W, double tanfovx, double tanfovy, double scale_modifier,
@@ -148,11 +219,9 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     const int64_t total_P = ragged ? means3D.size(0) : 0;
     const int64_t P = ragged ? max_P : (means3D.numel() > 0 ? means3D.size(-2) : 0);
     const int64_t M = shs.defined() ? shs.size(-2) : 0;
-    Tensor offsets;
+    const Tensor offsets = ragged ? *item_offsets_ : Tensor();
     if (ragged) {
-      offsets = *item_offsets_;
-      TORCH_CHECK(offsets.device() == dev && offsets.scalar_type() == at::kInt && offsets.is_contiguous() && offsets.numel() == n_items + 1,
-                  "item_offsets must be a contiguous int32 tensor of n_items + 1 prefix sums on the Gaussians' device");
+      check_item_offsets(offsets, dev, n_items + 1);
       TORCH_CHECK(!single && total_P > 0 && max_P > 0 && max_P <= total_P, "ragged batch: bad total / largest set size");
     }
     {
@@ -171,15 +240,8 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
       if (means2D_.has_value() && means2D_->defined())
         TORCH_CHECK(means2D_->numel() == (ragged ? vpi * total_P : (single ? P : NVc * P)) * 3, "means2D must be (views, P, 3)");
     }
-    u3d_raster_desc d{};
-    d.n_items = (int32_t)n_items; d.views_per_item = (int32_t)vpi; d.P = (int32_t)P;
-    d.image_height = (int32_t)H; d.image_width = (int32_t)W;
-    d.tanfovx = (float)tanfovx; d.tanfovy = (float)tanfovy; d.scale_modifier = (float)scale_modifier;
-    d.sh_degree = (int32_t)sh_degree; d.sh_coeffs = (int32_t)M; d.flags = (int32_t)flags;
-    d.total_P = (int32_t)total_P;
-    d.item_offsets = ragged ? offsets.data_ptr<int32_t>() : nullptr;
+    const u3d_raster_desc d = make_desc(n_items, vpi, P, H, W, tanfovx, tanfovy, scale_modifier, sh_degree, M, flags, total_P, offsets);
     const Plan plan = plan_for(d);
-    u3d_raster_desc dd = d;                                    // this call's descriptor: the plan's shape + the device pointer
     const int64_t NV = n_items * vpi;
     const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
     Tensor color = single ? at::empty({3, H, W}, fopt) : at::empty({NV, 3, H, W}, fopt);
@@ -188,40 +250,34 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     // malformed prefix-sum table leaves unprojected read as culled instead of as uninitialised memory)
     Tensor radii = single ? at::empty({P}, fopt.dtype(at::kInt))
                           : (ragged ? at::zeros({vpi * total_P}, fopt.dtype(at::kInt)) : at::empty({NV, P}, fopt.dtype(at::kInt)));
-    Tensor arena = at::empty({(int64_t)plan.fwd_scratch}, fopt.dtype(at::kByte));   // geom | binning | image
-    char* base = (char*)arena.data_ptr();
-    const int rc = u3d_rasterize_forward(&dd, fptr(bg), fptr(means3D), fptr(shs), fptr(colors), fptr(opac), fptr(scales), fptr(rots),
+    const ForwardArena arena(plan, ForwardArena::kImage, fopt.dtype(at::kByte));
+    const int rc = u3d_rasterize_forward(&d, fptr(bg), fptr(means3D), fptr(shs), fptr(colors), fptr(opac), fptr(scales), fptr(rots),
                                          fptr(cov), fptr(view), fptr(proj), fptr(campos), color.data_ptr<float>(), invdepth.data_ptr<float>(),
-                                         P > 0 ? radii.data_ptr<int32_t>() : nullptr, base, base + plan.o_binning, base + plan.o_image,
+                                         P > 0 ? radii.data_ptr<int32_t>() : nullptr, arena.geom(), arena.binning(), arena.tail(),
                                          current_stream(dev));
-    TORCH_CHECK(rc == U3D_OK, "u3d_rasterize_forward failed: ", u3d_error_string(rc), " (code ", rc, ")");
-    ctx->saved_data["plan"] = plan_save(plan);
-    ctx->saved_data["has_colors"] = colors.defined();
-    ctx->saved_data["single"] = single;
-    ctx->saved_data["has_means2D"] = means2D_.has_value() && means2D_->defined();
-    ctx->save_for_backward({means3D, shs, colors, opac, scales, rots, cov, view, proj, campos, bg, radii, arena, offsets});
+    check_rc(rc, "u3d_rasterize_forward");
+    ctx->saved_data["record"] = record_save(OpRecord{plan, single, means2D_.has_value() && means2D_->defined()});
+    ctx->save_for_backward({means3D, shs, colors, opac, scales, rots, cov, view, proj, campos, bg, radii, arena.buf, offsets});
     ctx->mark_non_differentiable({radii});
     ctx->set_materialize_grads(false);    // unused outputs (invdepth) arrive undefined, not as a zero tensor
     return {color, radii, invdepth};
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    const Plan plan = plan_load(ctx->saved_data["plan"].toStringRef());
-    const bool has_colors = ctx->saved_data["has_colors"].toBool();
-    const bool single = ctx->saved_data["single"].toBool();
-    const bool has_m2d = ctx->saved_data["has_means2D"].toBool();
+    const OpRecord r = record_load<OpRecord>(ctx->saved_data["record"]);
+    const Plan& plan = r.plan;
+    const bool single = r.single, has_m2d = r.has_means2D;
     auto sv = ctx->get_saved_variables();
-    const Tensor &means3D = sv[0], &shs = sv[1], &colors = sv[2], &opac = sv[3], &scales = sv[4], &rots = sv[5], &cov = sv[6], &view = sv[7],
-                 &proj = sv[8], &campos = sv[9], &bg = sv[10], &radii = sv[11], &arena = sv[12], &offsets = sv[13];
+    const Tensor &means3D = sv[kMeans3D], &shs = sv[kShs], &colors = sv[kColors], &opac = sv[kOpac], &scales = sv[kScales], &rots = sv[kRots],
+                 &cov = sv[kCov], &view = sv[kView], &proj = sv[kProj], &campos = sv[kCampos], &bg = sv[kBg], &radii = sv[kRadii],
+                 &offsets = sv[kOffsets];
     const bool ragged = offsets.defined();
     const u3d_raster_desc& d = plan.d;
     const c10::Device dev = means3D.device();
     const int64_t NV = (int64_t)d.n_items * d.views_per_item, P = d.P, M = d.sh_coeffs, n = d.n_items;
     const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
-    Tensor gcol = grads[0], ginv = grads[2];
-    if (gcol.defined()) gcol = f32c(gcol, dev);
-    else gcol = at::zeros({NV * 3, d.image_height, d.image_width}, fopt);     // only the inverse-depth output was used downstream
-    if (ginv.defined()) ginv = f32c(ginv, dev);
+    Tensor gcol = f32c(grads[0], dev), ginv = f32c(grads[2], dev);            // (undefined stays undefined)
+    if (!gcol.defined()) gcol = at::zeros({NV * 3, d.image_height, d.image_width}, fopt);     // only the inverse-depth output was used downstream
     const bool live = P > 0 && NV > 0;
     // the backward kernels write every element of every gradient they are handed (zeros for culled / untouched Gaussians)
     // gradient of a per-Gaussian input (per_view false) or of the per-(view, Gaussian) sink means2D (true), trailing dims `tail`:
@@ -238,31 +294,28 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     };
     Tensor g_means3D = out(false, {3}), g_means2D = has_m2d ? out(true, {3}) : Tensor(), g_op = out(false, {1});
     Tensor g_shs = shs.defined() ? out(false, {M, 3}) : Tensor();
-    Tensor g_col = has_colors ? out(false, {3}) : Tensor();
+    Tensor g_col = colors.defined() ? out(false, {3}) : Tensor();
     Tensor g_scales = scales.defined() ? out(false, {3}) : Tensor();
     Tensor g_rots = scales.defined() ? out(false, {4}) : Tensor();
     Tensor g_cov = cov.defined() ? out(false, {6}) : Tensor();
     if (live) {
       void* stream = current_stream(dev);
-      const WsKey key{(int)dev.index(), stream};
-      const std::string shape_key = desc_key(plan.d);
-      const Lease lease = workspace_acquire(key, plan, shape_key, fopt.dtype(at::kByte));
-      const Tensor& scratch = lease.buf;
-      u3d_raster_desc dd = plan.d;
-      dd.item_offsets = ragged ? offsets.data_ptr<int32_t>() : nullptr;
-      if (lease.clean) dd.flags |= U3D_FLAG_ACC_CLEAN;
-      const char* base = (const char*)arena.data_ptr();
+      ScopedLease lease(WsKey{(int)dev.index(), stream}, plan, fopt.dtype(at::kByte));
+      u3d_raster_desc dd = plan.d;                 // this call's descriptor: the plan's shape + this batch's device pointer
+      dd.item_offsets = offsets_ptr(offsets);
+      lease.apply_clean(dd);
+      const ForwardArena arena(plan, sv[kArena]);
       const int rc = u3d_rasterize_backward(&dd, fptr(bg), fptr(means3D), fptr(shs), fptr(colors), fptr(opac), fptr(scales), fptr(rots),
                                             fptr(cov), fptr(view), fptr(proj), fptr(campos), radii.data_ptr<int32_t>(), fptr(gcol), fptr(ginv),
-                                            base, base + plan.o_binning, base + plan.o_image, scratch.data_ptr(), fptr_mut(g_means3D),
+                                            arena.geom(), arena.binning(), arena.tail(), lease.buf.data_ptr(), fptr_mut(g_means3D),
                                             fptr_mut(g_means2D), fptr_mut(g_shs), fptr_mut(g_col), fptr_mut(g_op), fptr_mut(g_scales),
                                             fptr_mut(g_rots), fptr_mut(g_cov), stream);
-      if (rc != U3D_OK) workspace_release(key, lease.ticket, shape_key, false);
-      TORCH_CHECK(rc == U3D_OK, "u3d_rasterize_backward failed: ", u3d_error_string(rc), " (code ", rc, ")");
-      workspace_release(key, lease.ticket, shape_key);
+      check_rc(rc, "u3d_rasterize_backward");
+      lease.commit();
     }
-    return {g_means3D, g_means2D, g_shs, g_col, g_op, g_scales, g_rots, g_cov, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-            Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+    variable_list ret(24);    // one per forward argument; the per-Gaussian inputs come first
+    ret[0] = g_means3D; ret[1] = g_means2D; ret[2] = g_shs; ret[3] = g_col; ret[4] = g_op; ret[5] = g_scales; ret[6] = g_rots; ret[7] = g_cov;
+    return ret;
   }
 };
 
@@ -297,7 +350,7 @@ Tensor viewspace_sink(const Tensor& xyz) {
 }
 
 struct RenderViewFn : public torch::autograd::Function<RenderViewFn> {
-  using OptTensor = c10::optional<Tensor>;
+  enum Saved { kXyz, kDc, kRest, kOpac, kScales, kRots, kView, kProj, kCampos, kBg, kRadii, kArena };   // save_for_backward's order
   static variable_list forward(AutogradContext* ctx, Tensor xyz, Tensor sink, Tensor dc, OptTensor rest_, Tensor opac, Tensor scales,
                                Tensor rots, Tensor view, Tensor proj, Tensor campos, Tensor bg, int64_t H, int64_t W, double tanfovx,
                                double tanfovy, double scale_modifier, int64_t sh_degree, int64_t flags) {
@@ -311,35 +364,30 @@ struct RenderViewFn : public torch::autograd::Function<RenderViewFn> {
                     (!rest.defined() || rest.numel() == P * (M - 1) * 3),
                 "features_dc (P,1,3), features_rest (P,M-1,3), opacity (P,1), scaling (P,3), rotation (P,4) must match xyz (P,3)");
     TORCH_CHECK(view.numel() == 16 && proj.numel() == 16 && campos.numel() == 3 && bg.numel() == 3, "cameras must be (4,4), (4,4), (3,) and bg (3,)");
-    u3d_raster_desc d{};
-    d.n_items = 1; d.views_per_item = 1; d.P = (int32_t)P; d.image_height = (int32_t)H; d.image_width = (int32_t)W;
-    d.tanfovx = (float)tanfovx; d.tanfovy = (float)tanfovy; d.scale_modifier = (float)scale_modifier;
-    d.sh_degree = (int32_t)sh_degree; d.sh_coeffs = (int32_t)M; d.flags = (int32_t)flags;
+    const u3d_raster_desc d = make_desc(1, 1, P, H, W, tanfovx, tanfovy, scale_modifier, sh_degree, M, flags);
     const Plan plan = plan_for(d);
     const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
     Tensor color = at::empty({3, H, W}, fopt);
     Tensor radii = at::empty({P}, fopt.dtype(at::kInt));
     Tensor visible = at::empty({P}, fopt.dtype(at::kBool));
-    Tensor arena = at::empty({(int64_t)plan.fwd_scratch}, fopt.dtype(at::kByte));
-    char* base = (char*)arena.data_ptr();
-    u3d_raster_desc dd = d;
-    const int rc = u3d_render_view_forward(&dd, fptr(bg), fptr(xyz), fptr(dc), M > 1 ? fptr(rest) : nullptr, fptr(opac), fptr(scales), fptr(rots),
+    const ForwardArena arena(plan, ForwardArena::kImage, fopt.dtype(at::kByte));
+    const int rc = u3d_render_view_forward(&d, fptr(bg), fptr(xyz), fptr(dc), M > 1 ? fptr(rest) : nullptr, fptr(opac), fptr(scales), fptr(rots),
                                            fptr(view), fptr(proj), fptr(campos), color.data_ptr<float>(), P > 0 ? radii.data_ptr<int32_t>() : nullptr,
-                                           P > 0 ? (uint8_t*)visible.data_ptr() : nullptr, base, base + plan.o_binning, base + plan.o_image,
+                                           P > 0 ? (uint8_t*)visible.data_ptr() : nullptr, arena.geom(), arena.binning(), arena.tail(),
                                            current_stream(dev));
-    TORCH_CHECK(rc == U3D_OK, "u3d_render_view_forward failed: ", u3d_error_string(rc), " (code ", rc, ")");
-    ctx->saved_data["plan"] = plan_save(plan);
-    ctx->save_for_backward({xyz, dc, rest, opac, scales, rots, view, proj, campos, bg, radii, arena});
+    check_rc(rc, "u3d_render_view_forward");
+    ctx->saved_data["plan"] = record_save(plan);
+    ctx->save_for_backward({xyz, dc, rest, opac, scales, rots, view, proj, campos, bg, radii, arena.buf});
     ctx->mark_non_differentiable({radii, visible});
     ctx->set_materialize_grads(false);
     return {color, radii, visible};
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    const Plan plan = plan_load(ctx->saved_data["plan"].toStringRef());
+    const Plan plan = record_load<Plan>(ctx->saved_data["plan"]);
     auto sv = ctx->get_saved_variables();
-    const Tensor &xyz = sv[0], &dc = sv[1], &rest = sv[2], &opac = sv[3], &scales = sv[4], &rots = sv[5], &view = sv[6], &proj = sv[7],
-                 &campos = sv[8], &bg = sv[9], &radii = sv[10], &arena = sv[11];
+    const Tensor &xyz = sv[kXyz], &dc = sv[kDc], &rest = sv[kRest], &opac = sv[kOpac], &scales = sv[kScales], &rots = sv[kRots], &view = sv[kView],
+                 &proj = sv[kProj], &campos = sv[kCampos], &bg = sv[kBg], &radii = sv[kRadii];
     const u3d_raster_desc& d = plan.d;
     const c10::Device dev = xyz.device();
     const int64_t P = d.P, M = d.sh_coeffs;
@@ -351,19 +399,17 @@ struct RenderViewFn : public torch::autograd::Function<RenderViewFn> {
     Tensor g_rest = M > 1 ? at::empty({P, M - 1, 3}, fopt) : Tensor();
     Tensor g_op = at::empty({P, 1}, fopt), g_scales = at::empty({P, 3}, fopt), g_rots = at::empty({P, 4}, fopt);
     void* stream = current_stream(dev);
-    const WsKey key{(int)dev.index(), stream};
-    const std::string shape_key = desc_key(plan.d);
-    const Lease lease = workspace_acquire(key, plan, shape_key, fopt.dtype(at::kByte));
+    ScopedLease lease(WsKey{(int)dev.index(), stream}, plan, fopt.dtype(at::kByte));
     u3d_raster_desc dd = plan.d;
-    if (lease.clean) dd.flags |= U3D_FLAG_ACC_CLEAN;
-    const char* base = (const char*)arena.data_ptr();
+    lease.apply_clean(dd);
+    const ForwardArena arena(plan, sv[kArena]);
     const int rc = u3d_render_view_backward(&dd, fptr(bg), fptr(xyz), fptr(dc), M > 1 ? fptr(rest) : nullptr, fptr(opac), fptr(scales), fptr(rots),
-                                            fptr(view), fptr(proj), fptr(campos), radii.data_ptr<int32_t>(), fptr(gcol), base,
-                                            base + plan.o_binning, base + plan.o_image, lease.buf.data_ptr(), fptr_mut(g_xyz), fptr_mut(g_sink),
+                                            fptr(view), fptr(proj), fptr(campos), radii.data_ptr<int32_t>(), fptr(gcol), arena.geom(),
+                                            arena.binning(), arena.tail(), lease.buf.data_ptr(), fptr_mut(g_xyz), fptr_mut(g_sink),
                                             fptr_mut(g_dc), M > 1 ? fptr_mut(g_rest) : nullptr, fptr_mut(g_op), fptr_mut(g_scales),
                                             fptr_mut(g_rots), stream);
-    workspace_release(key, lease.ticket, shape_key, rc == U3D_OK);
-    TORCH_CHECK(rc == U3D_OK, "u3d_render_view_backward failed: ", u3d_error_string(rc), " (code ", rc, ")");
+    check_rc(rc, "u3d_render_view_backward");
+    lease.commit();
     out[0] = g_xyz; out[1] = g_sink; out[2] = g_dc; out[3] = g_rest; out[4] = g_op.view(opac.sizes()); out[5] = g_scales; out[6] = g_rots;
     return out;
   }
@@ -371,16 +417,15 @@ struct RenderViewFn : public torch::autograd::Function<RenderViewFn> {
 
 // (color (3,H,W), viewspace_points (P,3) leaf, radii (P,) int32, visibility_filter (P,) bool)
 std::tuple<Tensor, Tensor, Tensor, Tensor> render_view(const Tensor& xyz, const Tensor& opacity, const Tensor& scaling, const Tensor& rotation,
-                                                       const Tensor& features_dc, const c10::optional<Tensor>& features_rest, const Tensor& view,
+                                                       const Tensor& features_dc, const OptTensor& features_rest, const Tensor& view,
                                                        const Tensor& proj, const Tensor& campos, const Tensor& bg, int64_t H, int64_t W,
                                                        double tanfovx, double tanfovy, double scale_modifier, int64_t sh_degree, int64_t flags) {
   const c10::Device dev = xyz.device();
   const Tensor x = f32c(xyz, dev);
   Tensor sink = viewspace_sink(x);
-  c10::optional<Tensor> rest;
-  if (features_rest.has_value() && features_rest->defined() && features_rest->numel() > 0) rest = f32c(*features_rest, dev);
-  auto r = RenderViewFn::apply(x, sink, f32c(features_dc, dev), rest, f32c(opacity, dev), f32c(scaling, dev), f32c(rotation, dev), f32c(view, dev),
-                               f32c(proj, dev), f32c(campos, dev), f32c(bg, dev), H, W, tanfovx, tanfovy, scale_modifier, sh_degree, flags);
+  auto r = RenderViewFn::apply(x, sink, f32c(features_dc, dev), opt(features_rest, dev), f32c(opacity, dev), f32c(scaling, dev), f32c(rotation, dev),
+                               f32c(view, dev), f32c(proj, dev), f32c(campos, dev), f32c(bg, dev), H, W, tanfovx, tanfovy, scale_modifier, sh_degree,
+                               flags);
   return {r[0], sink, r[1], r[2]};
 }
 
@@ -388,20 +433,54 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> render_view(const Tensor& xyz, const 
 // One call per training step, but its host cost is exposed whenever a step's kernels are short (C1, C3: 7 launches in ~0.1 ms).
 std::mutex g_unit_mu;
 auto* g_unit = new std::map<int, Tensor>();   // (heap, never destroyed)
-Tensor unit_tensor(int64_t device_index) {   // the cached dL/dloss = 1 of fused.backward_unit(): recognised by its storage in backward
+// the cached dL/dloss = 1 of fused.backward_unit(): recognised by its storage in backward, which only looks it up (create false:
+// undefined when fused.backward_unit() has never asked for it)
+Tensor cached_unit(int device_index, bool create) {
   std::lock_guard<std::mutex> lock(g_unit_mu);
-  auto it = g_unit->find((int)device_index);
-  if (it == g_unit->end())
-    it = g_unit->emplace((int)device_index, at::ones({}, at::TensorOptions().dtype(at::kFloat).device(c10::Device(c10::kCUDA, (c10::DeviceIndex)device_index)))).first;
-  return it->second;
+  auto it = g_unit->find(device_index);
+  if (it != g_unit->end()) return it->second;
+  if (!create) return Tensor();
+  const auto opts = at::TensorOptions().dtype(at::kFloat).device(c10::Device(c10::kCUDA, (c10::DeviceIndex)device_index));
+  return g_unit->emplace(device_index, at::ones({}, opts)).first->second;
 }
+Tensor unit_tensor(int64_t device_index) { return cached_unit((int)device_index, true); }
+
+// what the step's node keeps besides tensors ("consumed" is its own entry: it changes after forward)
+// ticket: the lease taken in forward; stream: the one forward ran on
+struct StepRecord { Plan plan; u3d_head_desc head; u3d_loss_desc loss; uint64_t ticket; void* stream; };
+
+// (every row is written by the projection-backward kernel; a ragged batch starts from zeros so that rows a malformed prefix-sum
+// table leaves out read as zero gradient instead of as uninitialised memory, whichever route runs)
+inline Tensor new_d_head(const Tensor& head_out, bool ragged) { return ragged ? at::zeros_like(head_out) : at::empty_like(head_out); }
 
 struct RenderLossStepFn : public torch::autograd::Function<RenderLossStepFn> {
   // forward  = u3d_render_loss_step_forward : projection [+ sort] -> single-pass tile kernel -> fixed-order reduce  => loss + accumulators
   // backward = u3d_render_loss_step_backward: chain rule accumulators -> d(head_out), scaled IN the kernel by autograd's grad_output
   // (a device scalar): a plain `loss.backward()` (train_network.py:333) launches the same kernels as the one-call C entry point,
   // with no d_head * g multiply; fused.backward_unit() additionally spares autograd's ones_like fill.
-  using OptTensor = c10::optional<Tensor>;
+  // save_for_backward's order.  (What the node pins from forward to backward: the forward arena, the leased backward scratch, gt and
+  // bg -- see INTEGRATION.md "memory held between forward and backward".)
+  enum Saved { kHeadOut, kCenter, kView, kProj, kCampos, kRadii, kArena, kScratch, kOffsets, kGt, kBg, kDHead };
+
+  // The forward half into `lease`'s scratch, on the saved tensors `sv`: from autograd's forward, and again from a second backward (the
+  // recompute).  `d` is the descriptor without the lease's promise.  Returns the pre-allocated d(head_out), defined with
+  // U3D_FLAG_SPARSE_BWD only: scene-level head: the gradient buffer exists before the backward half (the flag is set by render_loss_step
+  // below): the forward half zero-fills it beside its gradient reduction and the backward half visits the touched Gaussians only.  The
+  // library honours the flag at scene-level sizes; below them the backward half writes every row itself, as before.
+  static Tensor forward_half(const char* what, const u3d_raster_desc& d, const StepRecord& r, const variable_list& sv, float* color, Tensor& loss,
+                             const ScopedLease& lease) {
+    u3d_raster_desc dd = d;
+    lease.apply_clean(dd);
+    const ForwardArena arena(r.plan, sv[kArena]);
+    Tensor d_head = (d.flags & U3D_FLAG_SPARSE_BWD) ? new_d_head(sv[kHeadOut], d.item_offsets != nullptr) : Tensor();
+    const int rc = u3d_render_loss_step_forward(&dd, &r.head, &r.loss, fptr(sv[kBg]), fptr(sv[kHeadOut]), fptr(sv[kCenter]), fptr(sv[kView]),
+                                                fptr(sv[kProj]), fptr(sv[kCampos]), fptr(sv[kGt]), color, sv[kRadii].data_ptr<int32_t>(),
+                                                loss.data_ptr<float>(), arena.geom(), arena.binning(), arena.tail(), lease.buf.data_ptr(),
+                                                d_head.defined() ? d_head.data_ptr<float>() : nullptr, r.stream);
+    check_rc(rc, what);
+    return d_head;
+  }
+
   static variable_list forward(AutogradContext* ctx, Tensor head_out, Tensor center, Tensor view, Tensor proj, Tensor campos, Tensor gt,
                                Tensor bg, int64_t H, int64_t W, double tanfov, int64_t mode, double offset_scale, int64_t sh_degree,
                                int64_t loss_kind, double non_bg_rate, double bg_rate, double scale_modifier, int64_t flags, bool want_color,
@@ -409,13 +488,11 @@ struct RenderLossStepFn : public torch::autograd::Function<RenderLossStepFn> {
     const c10::Device dev = head_out.device();
     TORCH_CHECK(dev.is_cuda(), "the MI355X rasterizer needs tensors on a HIP device; there is no CPU fallback");
     const bool ragged = item_offsets_.has_value() && item_offsets_->defined();
-    Tensor offsets;
+    const Tensor offsets = ragged ? *item_offsets_ : Tensor();
     int64_t B, P, C, total_P = 0;
     if (ragged) {
-      offsets = *item_offsets_;
       TORCH_CHECK(head_out.dim() == 2, "ragged batch: head_out must be packed (sum P_i, C)");
-      TORCH_CHECK(offsets.device() == dev && offsets.scalar_type() == at::kInt && offsets.is_contiguous(),
-                  "item_offsets must be a contiguous int32 tensor on the Gaussians' device");
+      check_item_offsets(offsets, dev);
       B = offsets.numel() - 1; total_P = head_out.size(0); C = head_out.size(1); P = max_P;
       TORCH_CHECK(P > 0 && P <= total_P, "ragged batch: max_P (the largest set) is required");
     } else {
@@ -432,63 +509,38 @@ struct RenderLossStepFn : public torch::autograd::Function<RenderLossStepFn> {
       TORCH_CHECK(view.numel() == NV * 16 && proj.numel() == NV * 16 && campos.numel() == NV * 3 && bg.numel() == 3 && gt.numel() == NV * 3 * H * W,
                   "cameras must be (views, 16), (views, 16), (views, 3), bg (3,) and gt (views, 3, H, W)");
     }
-    u3d_raster_desc d{};
-    d.n_items = (int32_t)B; d.views_per_item = (int32_t)V; d.P = (int32_t)P; d.image_height = (int32_t)H; d.image_width = (int32_t)W;
-    d.tanfovx = d.tanfovy = (float)tanfov; d.scale_modifier = (float)scale_modifier; d.sh_degree = (int32_t)sh_degree;
-    d.sh_coeffs = (int32_t)K; d.flags = (int32_t)flags; d.total_P = (int32_t)total_P;   // (U3D_FLAG_SPARSE_BWD: decided by render_loss_step below)
-    d.item_offsets = ragged ? offsets.data_ptr<int32_t>() : nullptr;
-    const Plan plan = plan_for(d);
-    u3d_head_desc hd{(int32_t)mode, (int32_t)C, (float)offset_scale, isotropic ? 1 : 0};
-    u3d_loss_desc ld{(int32_t)loss_kind, (float)non_bg_rate, (float)bg_rate};
+    // (flags: U3D_FLAG_SPARSE_BWD is decided by render_loss_step below)
+    const u3d_raster_desc d = make_desc(B, V, P, H, W, tanfov, tanfov, scale_modifier, sh_degree, K, flags, total_P, offsets);
+    StepRecord r{plan_for(d), u3d_head_desc{(int32_t)mode, (int32_t)C, (float)offset_scale, isotropic ? 1 : 0},
+                 u3d_loss_desc{(int32_t)loss_kind, (float)non_bg_rate, (float)bg_rate}, 0, current_stream(dev)};
     const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
     Tensor color = want_color ? at::empty({NV, 3, H, W}, fopt) : at::empty({0}, fopt);
     Tensor radii = ragged ? at::zeros({V * total_P}, fopt.dtype(at::kInt)) : at::empty({NV, P}, fopt.dtype(at::kInt));
     Tensor loss = at::empty({}, fopt);
-    const size_t o_fused = plan.o_image;                                 // arena: geom | binning | fused  (no image buffer in this path)
-    Tensor arena = at::empty({(int64_t)(o_fused + align256(plan.s.fused_bytes))}, fopt.dtype(at::kByte));
-    char* base = (char*)arena.data_ptr();
-    void* stream = current_stream(dev);
-    const WsKey key{(int)dev.index(), stream};
-    const std::string shape_key = desc_key(d);
-    const Lease lease = workspace_acquire(key, plan, shape_key, fopt.dtype(at::kByte));
-    u3d_raster_desc dd = d;
-    if (lease.clean) dd.flags |= U3D_FLAG_ACC_CLEAN;
-    // scene-level head: the gradient buffer exists before the backward half (U3D_FLAG_SPARSE_BWD, set in `d` by the caller below):
-    // the forward half zero-fills it beside its gradient reduction and the backward half visits the touched Gaussians only.  The
-    // library honours the flag at scene-level sizes; below them the backward half writes every row itself, as before.
-    // (ragged: from zeros, so that rows a malformed prefix-sum table leaves out read as zero gradient whichever route runs)
-    Tensor d_head = (d.flags & U3D_FLAG_SPARSE_BWD) ? (ragged ? at::zeros_like(head_out) : at::empty_like(head_out)) : Tensor();
-    const int rc = u3d_render_loss_step_forward(&dd, &hd, &ld, fptr(bg), fptr(head_out), fptr(center), fptr(view), fptr(proj), fptr(campos),
-                                                fptr(gt), want_color ? color.data_ptr<float>() : nullptr, radii.data_ptr<int32_t>(),
-                                                loss.data_ptr<float>(), base, base + plan.o_binning, base + o_fused, lease.buf.data_ptr(),
-                                                d_head.defined() ? d_head.data_ptr<float>() : nullptr, stream);
-    if (rc != U3D_OK) workspace_release(key, lease.ticket, shape_key, false);
-    TORCH_CHECK(rc == U3D_OK, "u3d_render_loss_step_forward failed: ", u3d_error_string(rc), " (code ", rc, ")");
-    // (the lease stays outstanding until the backward half has consumed -- and re-zeroed -- the accumulators)
-    ctx->saved_data["plan"] = plan_save(plan);
-    ctx->saved_data["head"] = std::vector<int64_t>{mode, C, isotropic ? 1 : 0};
-    ctx->saved_data["offset_scale"] = offset_scale;
-    ctx->saved_data["ticket"] = (int64_t)lease.ticket;
-    ctx->saved_data["stream"] = (int64_t)(intptr_t)stream;
+    const ForwardArena arena(r.plan, ForwardArena::kFused, fopt.dtype(at::kByte));
+    ScopedLease lease(WsKey{(int)dev.index(), r.stream}, r.plan, fopt.dtype(at::kByte));
+    variable_list saved{head_out, center, view, proj, campos, radii, arena.buf, lease.buf, offsets, gt, bg, Tensor()};   // enum Saved's order
+    saved[kDHead] = forward_half("u3d_render_loss_step_forward", d, r, saved, want_color ? color.data_ptr<float>() : nullptr, loss, lease);
+    r.ticket = lease.hold();   // (the lease stays outstanding until the backward half has consumed -- and re-zeroed -- the accumulators)
+    ctx->saved_data["record"] = record_save(r);
     ctx->saved_data["consumed"] = false;
-    ctx->saved_data["loss"] = std::vector<double>{(double)loss_kind, non_bg_rate, bg_rate};
-    ctx->save_for_backward({head_out, center, view, proj, campos, radii, arena, lease.buf, offsets, gt, bg, d_head});
+    ctx->save_for_backward(saved);
     ctx->mark_non_differentiable({color, radii});
     ctx->set_materialize_grads(false);
     return {loss, color, radii};
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    const Plan plan = plan_load(ctx->saved_data["plan"].toStringRef());
-    const auto hv = ctx->saved_data["head"].toIntVector();
-    uint64_t ticket = (uint64_t)ctx->saved_data["ticket"].toInt();
+    const StepRecord r = record_load<StepRecord>(ctx->saved_data["record"]);
+    const Plan& plan = r.plan;
+    uint64_t ticket = r.ticket;
     auto sv = ctx->get_saved_variables();
-    const Tensor &head_out = sv[0], &center = sv[1], &view = sv[2], &proj = sv[3], &campos = sv[4], &radii = sv[5], &arena = sv[6],
-                 &offsets = sv[8], &gt = sv[9], &bg = sv[10];
-    Tensor scratch = sv[7];
-    Tensor d_head_pre = sv[11];            // (U3D_FLAG_SPARSE_BWD: zero-filled by the forward half; used by ONE backward)
+    const Tensor &head_out = sv[kHeadOut], &center = sv[kCenter], &view = sv[kView], &proj = sv[kProj], &campos = sv[kCampos], &radii = sv[kRadii],
+                 &offsets = sv[kOffsets];
+    Tensor scratch = sv[kScratch];
+    Tensor d_head = sv[kDHead];            // (U3D_FLAG_SPARSE_BWD: zero-filled by the forward half; used by ONE backward)
     const c10::Device dev = head_out.device();
-    const WsKey key{(int)dev.index(), (void*)(intptr_t)ctx->saved_data["stream"].toInt()};
+    const WsKey key{(int)dev.index(), r.stream};
     const std::string shape_key = desc_key(plan.d);
     variable_list out(22);
     if (!grads[0].defined()) {                 // the loss was not used downstream: nothing to chain, and the accumulators stay dirty
@@ -502,39 +554,22 @@ struct RenderLossStepFn : public torch::autograd::Function<RenderLossStepFn> {
     void* stream = current_stream(dev);
     TORCH_CHECK(stream == key.second, "the fused render-loss step must be backpropagated on the stream its forward ran on");
     u3d_raster_desc dd = plan.d;
-    dd.item_offsets = offsets.defined() ? offsets.data_ptr<int32_t>() : nullptr;
-    u3d_head_desc hd{(int32_t)hv[0], (int32_t)hv[1], (float)ctx->saved_data["offset_scale"].toDouble(), (int32_t)hv[2]};
-    const char* base = (const char*)arena.data_ptr();
+    dd.item_offsets = offsets_ptr(offsets);
+    const ForwardArena arena(plan, sv[kArena]);
     if (ctx->saved_data["consumed"].toBool()) {
       // backward(retain_graph=True) followed by another backward: the first one consumed (and re-zeroed) the accumulators, so the
       // forward half is run again into a fresh lease -- same inputs, same arena, identical results; the rare path pays a recompute.
-      // (What the node DOES pin from forward to backward: the forward arena, the leased backward scratch, gt and bg -- see
-      // INTEGRATION.md "memory held between forward and backward".)
-      const auto lv = ctx->saved_data["loss"].toDoubleVector();
-      u3d_loss_desc ld{(int32_t)lv[0], (float)lv[1], (float)lv[2]};
-      const Lease lease = workspace_acquire(key, plan, shape_key, at::TensorOptions().dtype(at::kByte).device(dev));
-      u3d_raster_desc d2 = dd;
-      if (lease.clean) d2.flags |= U3D_FLAG_ACC_CLEAN;
+      // (the first backward handed its pre-allocated d(head_out) to autograd: the call makes a new one)
+      ScopedLease lease(key, plan, at::TensorOptions().dtype(at::kByte).device(dev));
       Tensor loss_again = at::empty({}, at::TensorOptions().dtype(at::kFloat).device(dev));
-      if (d_head_pre.defined()) d_head_pre = offsets.defined() ? at::zeros_like(head_out) : at::empty_like(head_out);   // (the first backward handed its buffer to autograd)
-      const int rc2 = u3d_render_loss_step_forward(&d2, &hd, &ld, fptr(bg), fptr(head_out), fptr(center), fptr(view), fptr(proj), fptr(campos),
-                                                   fptr(gt), nullptr, radii.data_ptr<int32_t>(), loss_again.data_ptr<float>(), (void*)base,
-                                                   (void*)(base + plan.o_binning), (void*)(base + plan.o_image), lease.buf.data_ptr(),
-                                                   d_head_pre.defined() ? d_head_pre.data_ptr<float>() : nullptr, stream);
-      if (rc2 != U3D_OK) workspace_release(key, lease.ticket, shape_key, false);
-      TORCH_CHECK(rc2 == U3D_OK, "u3d_render_loss_step_forward (recompute) failed: ", u3d_error_string(rc2), " (code ", rc2, ")");
+      d_head = forward_half("u3d_render_loss_step_forward (recompute)", dd, r, sv, nullptr, loss_again, lease);   // (forward's stream: checked above)
       scratch = lease.buf;
-      ticket = lease.ticket;
+      ticket = lease.hold();
     }
     ctx->saved_data["consumed"] = true;
-    Tensor unit;
-    {
-      std::lock_guard<std::mutex> lock(g_unit_mu);
-      auto it = g_unit->find((int)dev.index());
-      if (it != g_unit->end()) unit = it->second;
-    }
     // dL/dloss: a device scalar the projection-backward kernel multiplies in as it reads the accumulators; THE unit tensor of
     // fused.backward_unit() (recognised by its storage) needs no load at all
+    const Tensor unit = cached_unit((int)dev.index(), false);
     Tensor g = grads[0];
     const float* gptr = nullptr;
     if (!(unit.defined() && g.data_ptr() == unit.data_ptr())) {
@@ -542,14 +577,12 @@ struct RenderLossStepFn : public torch::autograd::Function<RenderLossStepFn> {
       TORCH_CHECK(g.numel() == 1, "gradient of the scalar loss must be a scalar");
       gptr = g.data_ptr<float>();
     }
-    // (every row is written by the projection-backward kernel; a ragged batch starts from zeros so that rows a malformed prefix-sum
-    // table leaves out read as zero gradient instead of as uninitialised memory)
-    Tensor d_head = d_head_pre.defined() ? d_head_pre : (offsets.defined() ? at::zeros_like(head_out) : at::empty_like(head_out));
-    const int rc = u3d_render_loss_step_backward(&dd, &hd, fptr(head_out), fptr(center), fptr(view), fptr(proj), fptr(campos),
-                                                 radii.data_ptr<int32_t>(), gptr, base, base + plan.o_binning, (void*)(base + plan.o_image),
+    if (!d_head.defined()) d_head = new_d_head(head_out, offsets.defined());
+    const int rc = u3d_render_loss_step_backward(&dd, &r.head, fptr(head_out), fptr(center), fptr(view), fptr(proj), fptr(campos),
+                                                 radii.data_ptr<int32_t>(), gptr, arena.geom(), arena.binning(), arena.tail(),
                                                  scratch.data_ptr(), d_head.data_ptr<float>(), stream);
-    workspace_release(key, ticket, shape_key, rc == U3D_OK);
-    TORCH_CHECK(rc == U3D_OK, "u3d_render_loss_step_backward failed: ", u3d_error_string(rc), " (code ", rc, ")");
+    workspace_release(key, ticket, shape_key, rc == U3D_OK);   // (the lease taken in forward, or by the recompute above)
+    check_rc(rc, "u3d_render_loss_step_backward");
     out[0] = d_head;
     return out;
   }
@@ -559,7 +592,7 @@ std::tuple<Tensor, Tensor, Tensor> render_loss_step(const Tensor& head_out, cons
                                                     const Tensor& campos, const Tensor& gt, const Tensor& bg, int64_t H, int64_t W, double tanfov,
                                                     int64_t mode, double offset_scale, int64_t sh_degree, int64_t loss_kind, double non_bg_rate,
                                                     double bg_rate, double scale_modifier, int64_t flags, bool want_color, bool isotropic,
-                                                    const c10::optional<Tensor>& item_offsets, int64_t max_P) {
+                                                    const OptTensor& item_offsets, int64_t max_P) {
   const c10::Device dev = head_out.device();
   const int64_t NV = view.numel() / 16;
   // U3D_FLAG_SPARSE_BWD (gradient buffer allocated in forward, touched list) is asked for only where the library honours it AND a
@@ -575,41 +608,36 @@ std::tuple<Tensor, Tensor, Tensor> render_loss_step(const Tensor& head_out, cons
   return {r[0], r[1], r[2]};
 }
 
-// empty tensors count as absent (upstream's convention for colors_precomp / cov3D_precomp); present ones become contiguous fp32 on `dev`
-inline c10::optional<Tensor> opt(const c10::optional<Tensor>& t, const c10::Device& dev) {
-  if (t.has_value() && t->defined() && t->numel() > 0) return f32c(*t, dev);
-  return c10::nullopt;
+// The operator's one `apply` (every tensor contiguous fp32 on the Gaussians' device).  rest: RasterizeFn::forward's arguments from n_items on.
+template <typename... Rest>
+std::tuple<Tensor, Tensor, Tensor> rasterize_apply(const Tensor& means3D, const OptTensor& means2D, const OptTensor& shs, const OptTensor& colors,
+                                                   const Tensor& opac, const OptTensor& scales, const OptTensor& rots, const OptTensor& cov,
+                                                   const Tensor& view, const Tensor& proj, const Tensor& campos, const Tensor& bg, Rest... rest) {
+  const c10::Device dev = means3D.device();
+  auto f = [&](const OptTensor& t) { return opt(t, dev); };
+  auto r = RasterizeFn::apply(f32c(means3D, dev), f(means2D), f(shs), f(colors), f32c(opac, dev), f(scales), f(rots), f(cov), f32c(view, dev),
+                              f32c(proj, dev), f32c(campos, dev), f32c(bg, dev), rest...);
+  return {r[0], r[1], r[2]};
 }
 
 // Batched form: leading dimension = sets for the Gaussian parameters, = views for cameras and outputs.
-std::tuple<Tensor, Tensor, Tensor> rasterize_batched(const Tensor& means3D, const c10::optional<Tensor>& means2D, const c10::optional<Tensor>& shs,
-                                                     const c10::optional<Tensor>& colors, const Tensor& opac, const c10::optional<Tensor>& scales,
-                                                     const c10::optional<Tensor>& rots, const c10::optional<Tensor>& cov, const Tensor& view,
-                                                     const Tensor& proj, const Tensor& campos, const Tensor& bg, int64_t n_items, int64_t vpi,
-                                                     int64_t H, int64_t W, double tanfovx, double tanfovy, double scale_modifier,
-                                                     int64_t sh_degree, int64_t flags, const c10::optional<Tensor>& item_offsets,
-                                                     int64_t max_P) {
-  const c10::Device dev = means3D.device();
-  auto f = [&](const c10::optional<Tensor>& t) { return opt(t, dev); };
-  auto r = RasterizeFn::apply(f32c(means3D, dev), f(means2D), f(shs), f(colors), f32c(opac, dev), f(scales), f(rots), f(cov), f32c(view, dev),
-                              f32c(proj, dev), f32c(campos, dev), f32c(bg, dev), n_items, vpi, H, W, tanfovx, tanfovy, scale_modifier, sh_degree,
-                              flags, false, item_offsets, max_P);
-  return {r[0], r[1], r[2]};
+std::tuple<Tensor, Tensor, Tensor> rasterize_batched(const Tensor& means3D, const OptTensor& means2D, const OptTensor& shs, const OptTensor& colors,
+                                                     const Tensor& opac, const OptTensor& scales, const OptTensor& rots, const OptTensor& cov,
+                                                     const Tensor& view, const Tensor& proj, const Tensor& campos, const Tensor& bg, int64_t n_items,
+                                                     int64_t vpi, int64_t H, int64_t W, double tanfovx, double tanfovy, double scale_modifier,
+                                                     int64_t sh_degree, int64_t flags, const OptTensor& item_offsets, int64_t max_P) {
+  return rasterize_apply(means3D, means2D, shs, colors, opac, scales, rots, cov, view, proj, campos, bg, n_items, vpi, H, W, tanfovx, tanfovy,
+                         scale_modifier, sh_degree, flags, false, item_offsets, max_P);
 }
 
 // One view: the reference's operator call (gaussian_renderer/__init__.py:89-97).  means3D (P,3), means2D (P,3) gradient sink,
 // shs (P,M,3) | colors (P,3), opacities (P,1), scales (P,3) + rotations (P,4) | cov3D (P,6); cameras (4,4), (4,4), (3,), bg (3,).
-std::tuple<Tensor, Tensor, Tensor> rasterize_view(const Tensor& means3D, const c10::optional<Tensor>& means2D, const c10::optional<Tensor>& shs,
-                                                  const c10::optional<Tensor>& colors, const Tensor& opac, const c10::optional<Tensor>& scales,
-                                                  const c10::optional<Tensor>& rots, const c10::optional<Tensor>& cov, const Tensor& view,
-                                                  const Tensor& proj, const Tensor& campos, const Tensor& bg, int64_t H, int64_t W,
-                                                  double tanfovx, double tanfovy, double scale_modifier, int64_t sh_degree, int64_t flags) {
-  const c10::Device dev = means3D.device();
-  auto f = [&](const c10::optional<Tensor>& t) { return opt(t, dev); };
-  auto r = RasterizeFn::apply(f32c(means3D, dev), f(means2D), f(shs), f(colors), f32c(opac, dev), f(scales), f(rots), f(cov), f32c(view, dev),
-                              f32c(proj, dev), f32c(campos, dev), f32c(bg, dev), 1, 1, H, W, tanfovx, tanfovy, scale_modifier, sh_degree, flags,
-                              true, c10::nullopt, 0);
-  return {r[0], r[1], r[2]};
+std::tuple<Tensor, Tensor, Tensor> rasterize_view(const Tensor& means3D, const OptTensor& means2D, const OptTensor& shs, const OptTensor& colors,
+                                                  const Tensor& opac, const OptTensor& scales, const OptTensor& rots, const OptTensor& cov,
+                                                  const Tensor& view, const Tensor& proj, const Tensor& campos, const Tensor& bg, int64_t H,
+                                                  int64_t W, double tanfovx, double tanfovy, double scale_modifier, int64_t sh_degree, int64_t flags) {
+  return rasterize_apply(means3D, means2D, shs, colors, opac, scales, rots, cov, view, proj, campos, bg, (int64_t)1, (int64_t)1, H, W, tanfovx,
+                         tanfovy, scale_modifier, sh_degree, flags, true, OptTensor(), (int64_t)0);
 }
 
 }  // namespace
