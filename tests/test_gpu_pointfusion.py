@@ -69,15 +69,27 @@ def _draws(ref_count, seed):
     return rng.integers(0, max(int(ref_count.max()), 1), len(ref_count)) if len(ref_count) else np.zeros(0, np.int64)
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 4095, 4097, 10_007])
-def test_grid_sample_sizes_with_replayed_draws(n):
+def _check_replayed_draws(n, spread):
     from unipre3d_amd.pointfusion import grid_sample
-    c = _rand_coord(n, n)
+    c = _rand_coord(n, n, spread)
     vox = R.voxelize(c.numpy(), c.numpy().min(0), 0.02)
     d = _draws(vox["count"], n)
     ref = R.grid_sample(c.numpy(), None, 0.02, d)
     out = grid_sample(c.to(DEV), 0.02, draws=torch.tensor(d), return_inverse=True)
     _check_sample(out, ref)
+    return ref
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 4095, 4097, 10_007])
+def test_grid_sample_sizes_with_replayed_draws(n):
+    _check_replayed_draws(n, 0.1)
+
+
+def test_grid_sample_above_1024_tiles():
+    """1024 * 4096 + 1 points = 1025 sort tiles (five trips of the digit scan, the last with one tile; two entries per thread of the
+    one-workgroup scan) in about 3.27 M voxels"""
+    ref = _check_replayed_draws(1024 * 4096 + 1, 4.0)
+    assert 3_000_000 < len(ref["index"]) < 1024 * 4096
 
 
 def test_grid_sample_edge_cases():

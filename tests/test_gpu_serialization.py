@@ -126,6 +126,17 @@ def test_dtypes_and_no_batch():
     _check_serialize(coord.long(), None, 9, ("z-trans", "hilbert"), None, "batch=None")
 
 
+def test_serialize_and_pool_above_1024_tiles():
+    """1024 * 4096 + 1 rows = 1025 sort tiles: the digit scan walks each digit's line in five trips of 256 tiles with a carry (the last
+    trip holds one tile), and the one-workgroup scan of the per-tile head counts owns two entries per thread, most threads past the end"""
+    N = 1024 * 4096 + 1
+    coord, batch = _points(N, 10, 2, 1025)
+    ref = R.serialize(coord, batch, 10, ("hilbert",))
+    got = _se().serialize(coord.to(DEV), batch.to(DEV), 10, ("hilbert",), batch_size=2)
+    _same(got, ref, "serialize, 1025 tiles")
+    _same(_se().pool_clusters(got[0], 1, depth=10, batch_size=2), R.pool_clusters(ref[0], 1), "pool_clusters, 1025 tiles")
+
+
 def test_two_calls_are_bit_identical():
     coord, batch = _points(9001, 12, 2, 21, spread=15)
     c, b = coord.to(DEV), batch.to(DEV)

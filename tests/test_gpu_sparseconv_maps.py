@@ -121,6 +121,38 @@ def test_row_counts(N, kind, k):
     _check(kind, k, 6, 32, idx, list(D), B)
 
 
+def test_maps_above_1024_tiles():
+    """1024 * 4096 + 1 rows = 1025 sort tiles: the digit scan walks each digit's line in five trips of 256 tiles with a carry (the last
+    trip holds one tile), and the one-workgroup scan of the per-tile head counts owns two entries per thread.  The strided map's answer
+    follows from np.unique of output site * 8 + tap (an even grid: no row is dropped)."""
+    from unipre3d_amd import sparseconv as sp
+    N, B, D, s = 1024 * 4096 + 1, 2, (192, 192, 192), 2
+    g = np.random.default_rng(1025)
+    idx = np.concatenate([g.integers(0, B, size=(N, 1)), g.integers(0, D[0], size=(N, 3))], 1)
+    rf, rn = R.chains_np(idx, D)
+    assert (rn >= 0).sum() > 100_000, "sites repeat"
+    idx_d = _t(idx, torch.int32)
+
+    m = sp.subm_map(idx_d, D, B, 1)
+    first, nxt = m.first.cpu().numpy(), m.next.cpu().numpy()
+    assert np.array_equal(first, rf) and np.array_equal(nxt, rn)
+    assert np.array_equal(m.table.cpu().numpy()[:, 0], first)
+    del m
+
+    O = [d // s for d in D]
+    out_site = ((idx[:, 0] * O[0] + idx[:, 1] // s) * O[1] + idx[:, 2] // s) * O[2] + idx[:, 3] // s
+    key = out_site * s ** 3 + ((idx[:, 1] % s) * s + idx[:, 2] % s) * s + idx[:, 3] % s
+    sites = np.unique(out_site)
+    present, lowest = np.unique(key, return_index=True)           # the first occurrence of a key: its lowest row
+    table = np.full((len(sites), s ** 3), -1, dtype=np.int64)
+    table[np.searchsorted(sites, present // s ** 3), present % s ** 3] = lowest
+    out_indices = np.stack([sites // (O[0] * O[1] * O[2]), sites // (O[1] * O[2]) % O[0], sites // O[2] % O[1], sites % O[2]], 1)
+    m = sp.down_map(idx_d, D, B, s)
+    assert m.out_shape == O and np.array_equal(m.out_indices.cpu().numpy(), out_indices)
+    assert np.array_equal(m.table.cpu().numpy(), table)
+    assert np.array_equal(m.first.cpu().numpy(), rf) and np.array_equal(m.next.cpu().numpy(), rn)
+
+
 # ---- long chains of rows on one site -------------------------------------------------------------------------------------------
 def _chain_sets():
     g = np.random.default_rng(11)

@@ -8,7 +8,7 @@
 #include <algorithm>
 
 #include "unipre3d_pointfusion.h"
-#include "u3d_util.h"
+#include "u3d_keysort.h"
 
 namespace {
 
@@ -20,7 +20,6 @@ constexpr int ITEMS = 16;            // rounds of NT elements per tile
 constexpr int TILE = NT * ITEMS;     // elements per workgroup in the tiled passes
 constexpr int SCAN_NT = 1024;        // the one-workgroup exclusive scan
 
-inline int n_tiles(int n) { return (n + TILE - 1) / TILE; }
 // passes of the 8-bit LSD sort: eight over the 64-bit key, then enough over the set index to order sets (0 for one set)
 inline int set_passes(int S) { int q = 0; while (q < 4 && (1ll << (8 * q)) < S) ++q; return q; }
 inline int final_buffer(int S) { return (8 + set_passes(S)) & 1; }
@@ -36,21 +35,19 @@ struct Scratch {   // carved out of the caller's buffer; every array sized for n
 
 size_t carve(void* base, int n_max, int S, Scratch* s) {
   const size_t n = (size_t)(n_max > 0 ? n_max : 1);
-  const size_t nb = (size_t)n_tiles((int)n);
-  size_t off = 0;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align256(bytes); return q; };
+  const size_t nb = (size_t)blocks((long long)n, TILE);
+  Carver c{(char*)base};
   Scratch t;
-  t.keys[0] = (unsigned long long*)take(n * 8);
-  t.keys[1] = (unsigned long long*)take(n * 8);
-  t.vals[0] = (uint32_t*)take(n * 4);
-  t.vals[1] = (uint32_t*)take(n * 4);
-  t.rank = (uint32_t*)take(n * 4);
-  t.starts = (uint32_t*)take((n + 1) * 4);
-  t.hist = (uint32_t*)take((nb + 1) * 256 * 4);   // + the 256 digit totals of a radix pass
-  t.setmax = (int32_t*)take((size_t)(S > 0 ? S : 1) * 4);
+  t.keys[0] = c.take<unsigned long long>(n * 8);
+  t.keys[1] = c.take<unsigned long long>(n * 8);
+  t.vals[0] = c.take<uint32_t>(n * 4);
+  t.vals[1] = c.take<uint32_t>(n * 4);
+  t.rank = c.take<uint32_t>(n * 4);
+  t.starts = c.take<uint32_t>((n + 1) * 4);
+  t.hist = c.take<uint32_t>((nb + 1) * 256 * 4);   // + the 256 digit totals of a radix pass
+  t.setmax = c.take<int32_t>((size_t)(S > 0 ? S : 1) * 4);
   if (s) *s = t;
-  return off;
+  return c.off;
 }
 
 // set of point i: the largest s with off[s] <= i (empty sets are skipped over)
@@ -135,7 +132,7 @@ __global__ void minmax_decode_kernel(int S, int* __restrict__ mm) {
   if (t < 6 * S) reinterpret_cast<float*>(mm)[t] = o2f(mm[t]);
 }
 
-// ---- order-preserving flag scan: per-tile counts -> one-workgroup exclusive scan -> ranked emission ------------------------------
+// ---- the two uses of the flag ranking (flag_count_kernel -> scan_kernel -> flag_apply_kernel, u3d_keysort.h) -----------------------
 struct CompactOp {   // keep pixel i: w != 0 (NaN is valid, as torch's .bool()) and the inclusive box
   const float* uc4; const float* box; float* coord_out; int32_t* src_out;
   __device__ bool flag(uint32_t i) const {
@@ -160,73 +157,6 @@ struct HeadOp {      // segment heads of the sorted (set, key) sequence; rank = 
     if (f) starts[r] = i;
   }
 };
-
-template <class Op>
-__global__ __launch_bounds__(NT) void flag_count_kernel(Op op, int n_fixed, const int32_t* __restrict__ n_dev, uint32_t* __restrict__ cnt) {
-  const uint32_t n = n_fixed >= 0 ? (uint32_t)n_fixed : (uint32_t)*n_dev;
-  const uint32_t base = blockIdx.x * (uint32_t)TILE;
-  uint32_t c = 0;
-  for (int r = 0; r < ITEMS; ++r) {
-    const uint32_t i = base + r * NT + threadIdx.x;
-    if (i < n && op.flag(i)) ++c;
-  }
-  for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
-  __shared__ uint32_t part[NW];
-  if (lane_id() == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < NW; ++w) t += part[w];
-    cnt[blockIdx.x] = t;
-  }
-}
-
-// exclusive scan of L counts in place by ONE workgroup; the total goes to *total when total != NULL
-__global__ __launch_bounds__(SCAN_NT) void scan_kernel(int L, uint32_t* __restrict__ v, int32_t* __restrict__ total) {
-  const int t = threadIdx.x;
-  const int ch = (L + SCAN_NT - 1) / SCAN_NT;
-  const int b = t * ch, e = min(L, b + ch);
-  uint32_t s = 0;
-  for (int i = b; i < e; ++i) s += v[i];
-  // inclusive scan of the per-thread sums: inside each wave by shuffles, then over the 16 wave totals
-  __shared__ uint32_t wt[SCAN_NT / 64];
-  const uint32_t lane = lane_id();
-  uint32_t inc = s;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = (uint32_t)__shfl_up((int)inc, o);
-    if ((int)lane >= o) inc += u;
-  }
-  if (lane == 63) wt[t >> 6] = inc;
-  __syncthreads();
-  uint32_t run = inc - s;
-  for (int w = 0; w < (t >> 6); ++w) run += wt[w];
-  for (int i = b; i < e; ++i) { const uint32_t x = v[i]; v[i] = run; run += x; }
-  if (t == SCAN_NT - 1 && total) *total = (int32_t)run;
-}
-
-template <class Op>
-__global__ __launch_bounds__(NT) void flag_apply_kernel(Op op, int n_fixed, const int32_t* __restrict__ n_dev, const uint32_t* __restrict__ excl) {
-  const uint32_t n = n_fixed >= 0 ? (uint32_t)n_fixed : (uint32_t)*n_dev;
-  const uint32_t base = blockIdx.x * (uint32_t)TILE;
-  if (base >= n) return;
-  __shared__ uint32_t wc[NW];
-  const int wave = threadIdx.x >> 6;
-  const uint32_t lane = lane_id();
-  uint32_t run = excl[blockIdx.x];
-  for (int r = 0; r < ITEMS; ++r) {
-    const uint32_t i = base + r * NT + threadIdx.x;
-    const bool valid = i < n;
-    const bool f = valid && op.flag(i);
-    const unsigned long long m = __ballot(f);
-    if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t before = run, all = 0;
-    for (int w = 0; w < NW; ++w) { if (w < wave) before += wc[w]; all += wc[w]; }
-    if (valid) op.emit(i, before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)), f);
-    run += all;
-    __syncthreads();
-  }
-}
 
 // ---- keys and the stable LSD radix sort of (set, key, index) -------------------------------------------------------------
 __global__ __launch_bounds__(NT) void key_kernel(int n_fixed, const int32_t* __restrict__ n_dev, int S, const int32_t* __restrict__ off,
@@ -261,66 +191,25 @@ __global__ __launch_bounds__(NT) void radix_hist_kernel(int pass, const int32_t*
   hist[(size_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];   // digit-major: one exclusive scan gives every (digit, tile) its base
 }
 
-// Exclusive scan of one digit's row of tile counts (digit-major layout: one workgroup per digit, coalesced), its total to tot[digit];
-// the scatter adds the exclusive prefix of the 256 totals.  (One workgroup scanning all 256 x tiles entries took ~0.1 ms per pass at
-// 2.4 M points.)
-__global__ __launch_bounds__(NT) void row_scan_kernel(int nb, uint32_t* __restrict__ hist, uint32_t* __restrict__ tot) {
-  __shared__ uint32_t wt[NW];
-  uint32_t* row = hist + (size_t)blockIdx.x * nb;
-  uint32_t carry = 0;
-  for (int b0 = 0; b0 < nb; b0 += NT) {
-    const int b = b0 + threadIdx.x;
-    const uint32_t x = b < nb ? row[b] : 0u;
-    uint32_t all;
-    const uint32_t e = block_excl_scan<NW>(x, wt, all);
-    if (b < nb) row[b] = carry + e;
-    carry += all;
-  }
-  if (threadIdx.x == 0) tot[blockIdx.x] = carry;
-}
-
 // Stable scatter of one tile: rounds of NT elements ranked with the ballot multi-split (element order = round, wave, lane);
 // the per-wave digit counts become destinations through one prefix over the waves (the block radix sort of u3d_sort.hip, over HBM).
 __global__ __launch_bounds__(NT) void radix_scatter_kernel(int pass, const int32_t* __restrict__ n_dev, int nb,
                                                            const int32_t* __restrict__ off, int S, const uint32_t* __restrict__ hist,
-                                                           const uint32_t* __restrict__ tot, const unsigned long long* __restrict__ kin, const uint32_t* __restrict__ vin,
+                                                           const unsigned long long* __restrict__ kin, const uint32_t* __restrict__ vin,
                                                            unsigned long long* __restrict__ kout, uint32_t* __restrict__ vout) {
-  __shared__ uint32_t digit_base[256];
-  __shared__ uint32_t wave_cnt[NW][256];
-  __shared__ uint32_t wt[NW];
+  __shared__ RadixLds<NW> lds;
   const uint32_t n = (uint32_t)*n_dev;
   const uint32_t base = blockIdx.x * (uint32_t)TILE;
   if (base >= n) return;
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const uint32_t lane = lane_id();
-  uint32_t all;
-  digit_base[tid] = block_excl_scan<NW>(tot[tid], wt, all) + hist[(size_t)tid * nb + blockIdx.x];
+  radix_bases<NW>(lds, hist, hist + (size_t)nb * 256, nb);
   for (int r = 0; r < ITEMS; ++r) {
-    for (int w = 0; w < NW; ++w) wave_cnt[w][tid] = 0;
-    __syncthreads();
-    const uint32_t i = base + r * NT + tid;
+    radix_round_begin<NW>(lds);
+    const uint32_t i = base + r * NT + threadIdx.x;
     const bool valid = i < n;
     unsigned long long k = 0; uint32_t v = 0, digit = 0;
     if (valid) { k = kin[i]; v = vin[i]; digit = digit_of(pass, k, v, off, S); }
-    unsigned long long same = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (digit >> b) & 1u;
-      const unsigned long long m = __ballot(bit);
-      same &= bit ? m : ~m;
-    }
-    const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-    if (valid && rank == 0) wave_cnt[wave][digit] = (uint32_t)__popcll(same);
-    __syncthreads();
-    {   // counts -> destination of each wave's first element of the digit; digit_base moves past the round
-      uint32_t run = digit_base[tid];
-#pragma unroll
-      for (int w = 0; w < NW; ++w) { const uint32_t c = wave_cnt[w][tid]; wave_cnt[w][tid] = run; run += c; }
-      digit_base[tid] = run;
-    }
-    __syncthreads();
+    const uint32_t dst = radix_round_dst<NW>(lds, valid, digit);
     if (valid) {
-      const uint32_t dst = wave_cnt[wave][digit] + rank;
       kout[dst] = k;
       vout[dst] = v;
     }
@@ -474,11 +363,11 @@ int u3d_pointfusion_compact(int P, const float* uc4, const float* box, float* co
     (void)hipMemsetAsync(meta, 0, 4 * sizeof(int32_t), st);
     return launched();
   }
-  const int nb = n_tiles(P);
+  const int nb = blocks(P, TILE);
   CompactOp op{uc4, box, coord_out, src_out};
-  flag_count_kernel<CompactOp><<<nb, NT, 0, st>>>(op, P, nullptr, s.hist);
-  scan_kernel<<<1, SCAN_NT, 0, st>>>(nb, s.hist, meta);
-  flag_apply_kernel<CompactOp><<<nb, NT, 0, st>>>(op, P, nullptr, s.hist);
+  flag_count_kernel<NT, ITEMS, CompactOp><<<nb, NT, 0, st>>>(op, P, nullptr, s.hist);
+  scan_kernel<SCAN_NT><<<1, SCAN_NT, 0, st>>>(nb, s.hist, meta);
+  flag_apply_kernel<NT, ITEMS, CompactOp><<<nb, NT, 0, st>>>(op, P, nullptr, s.hist);
   return launched();
 }
 
@@ -492,20 +381,20 @@ int u3d_pointfusion_voxelize(int n_max, int n, int n_sets, const int32_t* set_of
   carve(scratch, n_max, n_sets, &s);
   setup_kernel<<<blocks(n_sets + 1, NT), NT, 0, st>>>(n, meta, n_sets, s.setmax);
   if (n_max > 0) {
-    const int nb = n_tiles(n_max);
+    const int nb = blocks(n_max, TILE);
     key_kernel<<<blocks(n_max, NT), NT, 0, st>>>(-1, meta, n_sets, set_offsets, coord, min_coord, min_stride, grid_size, s.keys[0], s.vals[0]);
     const int passes = 8 + set_passes(n_sets);
     for (int p = 0; p < passes; ++p) {
       const int a = p & 1;
       radix_hist_kernel<<<nb, NT, 0, st>>>(p, meta, nb, set_offsets, n_sets, s.keys[a], s.vals[a], s.hist);
-      row_scan_kernel<<<256, NT, 0, st>>>(nb, s.hist, s.hist + (size_t)nb * 256);
-      radix_scatter_kernel<<<nb, NT, 0, st>>>(p, meta, nb, set_offsets, n_sets, s.hist, s.hist + (size_t)nb * 256, s.keys[a], s.vals[a], s.keys[a ^ 1], s.vals[a ^ 1]);
+      digit_scan_kernel<NT><<<256, NT, 0, st>>>(nb, s.hist);
+      radix_scatter_kernel<<<nb, NT, 0, st>>>(p, meta, nb, set_offsets, n_sets, s.hist, s.keys[a], s.vals[a], s.keys[a ^ 1], s.vals[a ^ 1]);
     }
     const int fb = final_buffer(n_sets);
     HeadOp op{s.keys[fb], s.vals[fb], set_offsets, n_sets, s.rank, s.starts};
-    flag_count_kernel<HeadOp><<<nb, NT, 0, st>>>(op, -1, meta, s.hist);
-    scan_kernel<<<1, SCAN_NT, 0, st>>>(nb, s.hist, meta + 1);
-    flag_apply_kernel<HeadOp><<<nb, NT, 0, st>>>(op, -1, meta, s.hist);
+    flag_count_kernel<NT, ITEMS, HeadOp><<<nb, NT, 0, st>>>(op, -1, meta, s.hist);
+    scan_kernel<SCAN_NT><<<1, SCAN_NT, 0, st>>>(nb, s.hist, meta + 1);
+    flag_apply_kernel<NT, ITEMS, HeadOp><<<nb, NT, 0, st>>>(op, -1, meta, s.hist);
     finish_kernel<<<blocks(n_sets + 1, NT), NT, 0, st>>>(meta, n_sets, set_offsets, s.rank, s.starts, voxel_offsets);
     count_max_kernel<<<blocks(n_max, NT), NT, 0, st>>>(meta, n_sets, set_offsets, s.starts, s.vals[fb], s.setmax);
   } else {

@@ -6,7 +6,7 @@
 #include <stdint.h>
 
 #include "unipre3d_serialization.h"
-#include "u3d_util.h"
+#include "u3d_keysort.h"
 
 namespace {
 
@@ -20,8 +20,6 @@ constexpr int ITEMS = 16;            // rounds of NT elements per tile of the so
 constexpr int TILE = NT * ITEMS;
 constexpr int SCAN_NT = 1024;        // the one-workgroup exclusive scan
 
-inline int n_tiles(int n) { return (n + TILE - 1) / TILE; }
-
 struct Scratch {   // carved out of the caller's buffer for K rows of n elements
   u64* keys[2];
   uint32_t* vals[2];
@@ -31,19 +29,17 @@ struct Scratch {   // carved out of the caller's buffer for K rows of n elements
 
 size_t carve(void* base, int K, int n_rows, Scratch* s) {
   const size_t n = (size_t)(n_rows > 0 ? n_rows : 1), k = (size_t)(K > 0 ? K : 1);
-  const size_t nb = (size_t)n_tiles((int)n);
-  size_t off = 0;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align256(bytes); return q; };
+  const size_t nb = (size_t)blocks((long long)n, TILE);
+  Carver c{(char*)base};
   Scratch t;
-  t.keys[0] = (u64*)take(k * n * 8);
-  t.keys[1] = (u64*)take(k * n * 8);
-  t.vals[0] = (uint32_t*)take(k * n * 4);
-  t.vals[1] = (uint32_t*)take(k * n * 4);
-  t.rank = (uint32_t*)take(n * 4);
-  t.hist = (uint32_t*)take(k * (nb + 1) * 256 * 4);
+  t.keys[0] = c.take<u64>(k * n * 8);
+  t.keys[1] = c.take<u64>(k * n * 8);
+  t.vals[0] = c.take<uint32_t>(k * n * 4);
+  t.vals[1] = c.take<uint32_t>(k * n * 4);
+  t.rank = c.take<uint32_t>(n * 4);
+  t.hist = c.take<uint32_t>(k * (nb + 1) * 256 * 4);
   if (s) *s = t;
-  return off;
+  return c.off;
 }
 
 // ---- codes -----------------------------------------------------------------------------------------------------------------------
@@ -114,22 +110,6 @@ __global__ __launch_bounds__(NT) void radix_hist_kernel(int shift, int pre, int 
   hist[(size_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];
 }
 
-__global__ __launch_bounds__(NT) void digit_scan_kernel(int nb, uint32_t* __restrict__ hist) {   // grid (256 digits, K rows)
-  __shared__ uint32_t wt[NW];
-  hist += (size_t)blockIdx.y * (nb + 1) * 256;
-  uint32_t* line = hist + (size_t)blockIdx.x * nb;
-  uint32_t carry = 0;
-  for (int b0 = 0; b0 < nb; b0 += NT) {
-    const int b = b0 + threadIdx.x;
-    const uint32_t x = b < nb ? line[b] : 0u;
-    uint32_t all;
-    const uint32_t e = block_excl_scan<NW>(x, wt, all);
-    if (b < nb) line[b] = carry + e;
-    carry += all;
-  }
-  if (threadIdx.x == 0) hist[(size_t)nb * 256 + blockIdx.x] = carry;
-}
-
 // stable scatter of one tile: rounds of NT elements ranked by the ballot multi-split (element order = round, wave, lane).
 // FIRST: the index of an element is its position (no vin).  FINAL: writes order (the index, widened) and inverse, not (kout, vout).
 template <bool FIRST, bool FINAL>
@@ -137,43 +117,20 @@ __global__ __launch_bounds__(NT) void radix_scatter_kernel(int shift, int pre, i
                                                            size_t kstride, const u64* __restrict__ kin, const uint32_t* __restrict__ vin,
                                                            u64* __restrict__ kout, uint32_t* __restrict__ vout,
                                                            long long* __restrict__ order, long long* __restrict__ inverse) {
-  __shared__ uint32_t digit_base[256];
-  __shared__ uint32_t wave_cnt[NW][256];
-  __shared__ uint32_t wt[NW];
+  __shared__ RadixLds<NW> lds;
   const size_t row = (size_t)blockIdx.y * n;
   kin += kstride * blockIdx.y;
   hist += (size_t)blockIdx.y * (nb + 1) * 256;
   const uint32_t base = blockIdx.x * (uint32_t)TILE;
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const uint32_t lane = lane_id();
-  uint32_t all;
-  digit_base[tid] = block_excl_scan<NW>(hist[(size_t)nb * 256 + tid], wt, all) + hist[(size_t)tid * nb + blockIdx.x];
+  radix_bases<NW>(lds, hist, hist + (size_t)nb * 256, nb);
   for (int r = 0; r < ITEMS; ++r) {
-    for (int w = 0; w < NW; ++w) wave_cnt[w][tid] = 0;
-    __syncthreads();
-    const uint32_t i = base + r * NT + tid;
+    radix_round_begin<NW>(lds);
+    const uint32_t i = base + r * NT + threadIdx.x;
     const bool valid = i < (uint32_t)n;
     u64 k = 0; uint32_t v = 0, digit = 0;
     if (valid) { k = kin[i]; v = FIRST ? i : vin[row + i]; digit = digit_of(k, shift, pre); }
-    u64 same = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (digit >> b) & 1u;
-      const u64 m = __ballot(bit);
-      same &= bit ? m : ~m;
-    }
-    const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-    if (valid && rank == 0) wave_cnt[wave][digit] = (uint32_t)__popcll(same);
-    __syncthreads();
-    {
-      uint32_t run = digit_base[tid];
-#pragma unroll
-      for (int w = 0; w < NW; ++w) { const uint32_t c = wave_cnt[w][tid]; wave_cnt[w][tid] = run; run += c; }
-      digit_base[tid] = run;
-    }
-    __syncthreads();
+    const uint32_t dst = radix_round_dst<NW>(lds, valid, digit);
     if (valid) {
-      const uint32_t dst = wave_cnt[wave][digit] + rank;   // < n: the bases are an exclusive scan of counts that sum to n
       if (FINAL) {
         order[row + dst] = (long long)v;
         inverse[row + v] = (long long)dst;
@@ -190,7 +147,7 @@ __global__ __launch_bounds__(NT) void radix_scatter_kernel(int shift, int pre, i
 // otherwise the result is (keys[b], vals[b]) with b the returned buffer.  Keys move unshifted.
 int radix_sort(const Scratch& s, int K, int n, int key_bits, int pre, const u64* src, bool final, long long* order, long long* inverse,
                hipStream_t st) {
-  const int nb = n_tiles(n), passes = (key_bits + 7) / 8;
+  const int nb = blocks(n, TILE), passes = (key_bits + 7) / 8;
   const dim3 gt(nb, K), gs(256, K);
   const size_t ks = (size_t)n;
   for (int p = 0; p < passes; ++p) {
@@ -200,7 +157,7 @@ int radix_sort(const Scratch& s, int K, int n, int key_bits, int pre, const u64*
     uint32_t* vout = s.vals[p & 1];
     const bool last = final && p == passes - 1;
     radix_hist_kernel<<<gt, NT, 0, st>>>(8 * p, pre, n, nb, ks, kin, s.hist);
-    digit_scan_kernel<<<gs, NT, 0, st>>>(nb, s.hist);
+    digit_scan_kernel<NT><<<gs, NT, 0, st>>>(nb, s.hist);
     if (p == 0 && last)
       radix_scatter_kernel<true, true><<<gt, NT, 0, st>>>(8 * p, pre, n, nb, s.hist, ks, kin, vin, kout, vout, order, inverse);
     else if (p == 0)
@@ -253,68 +210,11 @@ __device__ __forceinline__ bool is_head(const u64* keys, int j, int shift) {
   return j == 0 || (keys[j] >> shift) != (keys[j - 1] >> shift);
 }
 
-__global__ __launch_bounds__(NT) void head_count_kernel(int n, int shift, const u64* __restrict__ keys, uint32_t* __restrict__ cnt) {
-  const uint32_t base = blockIdx.x * (uint32_t)TILE;
-  uint32_t c = 0;
-  for (int r = 0; r < ITEMS; ++r) {
-    const uint32_t i = base + r * NT + threadIdx.x;
-    if (i < (uint32_t)n && is_head(keys, (int)i, shift)) ++c;
-  }
-  for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
-  __shared__ uint32_t part[NW];
-  if (lane_id() == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < NW; ++w) t += part[w];
-    cnt[blockIdx.x] = t;
-  }
-}
-
-// exclusive scan of L counts in place by ONE workgroup; the total goes to *total
-__global__ __launch_bounds__(SCAN_NT) void scan_kernel(int L, uint32_t* __restrict__ v, int32_t* __restrict__ total) {
-  const int t = threadIdx.x;
-  const int ch = (L + SCAN_NT - 1) / SCAN_NT;
-  const int b = min(L, t * ch), e = min(L, b + ch);
-  uint32_t s = 0;
-  for (int i = b; i < e; ++i) s += v[i];
-  __shared__ uint32_t wt[SCAN_NT / 64];
-  const uint32_t lane = lane_id();
-  uint32_t inc = s;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = (uint32_t)__shfl_up((int)inc, o);
-    if ((int)lane >= o) inc += u;
-  }
-  if (lane == 63) wt[t >> 6] = inc;
-  __syncthreads();
-  uint32_t run = inc - s;
-  for (int w = 0; w < (t >> 6); ++w) run += wt[w];
-  for (int i = b; i < e; ++i) { const uint32_t x = v[i]; v[i] = run; run += x; }
-  if (t == SCAN_NT - 1) *total = (int32_t)run;
-}
-
-// rank[j] = cluster of sorted position j (heads up to and including j, minus one)
-__global__ __launch_bounds__(NT) void head_rank_kernel(int n, int shift, const u64* __restrict__ keys, const uint32_t* __restrict__ excl,
-                                                       uint32_t* __restrict__ rank) {
-  const uint32_t base = blockIdx.x * (uint32_t)TILE;
-  __shared__ uint32_t wc[NW];
-  const int wave = threadIdx.x >> 6;
-  const uint32_t lane = lane_id();
-  uint32_t run = excl[blockIdx.x];
-  for (int r = 0; r < ITEMS; ++r) {
-    const uint32_t i = base + r * NT + threadIdx.x;
-    const bool valid = i < (uint32_t)n;
-    const bool f = valid && is_head(keys, (int)i, shift);
-    const u64 m = __ballot(f);
-    if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t before = run, all = 0;
-    for (int w = 0; w < NW; ++w) { if (w < wave) before += wc[w]; all += wc[w]; }
-    if (valid) rank[i] = before + (uint32_t)__popcll(m & ((2ull << lane) - 1ull)) - 1u;
-    run += all;
-    __syncthreads();
-  }
-}
+struct ClusterOp {   // heads of the sorted keys >> shift; rank = cluster of each sorted position
+  const u64* keys; int shift; uint32_t* rank;
+  __device__ bool flag(uint32_t i) const { return is_head(keys, (int)i, shift); }
+  __device__ void emit(uint32_t i, uint32_t r, bool f) const { rank[i] = f ? r : r - 1u; }   // r = heads before i
+};
 
 __global__ __launch_bounds__(NT) void pool_emit_kernel(int K, int n, int M, int shift, const long long* __restrict__ code,
                                                        const u64* __restrict__ keys, const uint32_t* __restrict__ vals,
@@ -388,10 +288,11 @@ int u3d_ser_pool_count(int K, int N, int shift, int key_bits, const int64_t* cod
   Scratch s;
   carve(scratch, K, N, &s);
   const int fb = radix_sort(s, 1, N, key_bits, shift, (const u64*)code, false, nullptr, nullptr, st);
-  const int nb = n_tiles(N);
-  head_count_kernel<<<nb, NT, 0, st>>>(N, shift, s.keys[fb], s.hist);
-  scan_kernel<<<1, SCAN_NT, 0, st>>>(nb, s.hist, meta);
-  head_rank_kernel<<<nb, NT, 0, st>>>(N, shift, s.keys[fb], s.hist, s.rank);
+  const int nb = blocks(N, TILE);
+  const ClusterOp op{s.keys[fb], shift, s.rank};
+  flag_count_kernel<NT, ITEMS, ClusterOp><<<nb, NT, 0, st>>>(op, N, nullptr, s.hist);
+  scan_kernel<SCAN_NT><<<1, SCAN_NT, 0, st>>>(nb, s.hist, meta);
+  flag_apply_kernel<NT, ITEMS, ClusterOp><<<nb, NT, 0, st>>>(op, N, nullptr, s.hist);
   return launched();
 }
 

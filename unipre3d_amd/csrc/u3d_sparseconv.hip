@@ -7,7 +7,7 @@
 #include <algorithm>
 
 #include "unipre3d_sparseconv.h"
-#include "u3d_util.h"
+#include "u3d_keysort.h"
 
 namespace {
 
@@ -23,7 +23,6 @@ constexpr int SMALL_C = 8;           // a channel count at or below this takes t
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-inline int n_tiles(int n) { return (n + TILE - 1) / TILE; }
 inline int bit_len(unsigned long long v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
 
 struct Scratch {   // carved out of the caller's buffer; every array sized for n rows
@@ -36,20 +35,18 @@ struct Scratch {   // carved out of the caller's buffer; every array sized for n
 
 size_t carve(void* base, int n_rows, Scratch* s) {
   const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
-  const size_t nb = (size_t)n_tiles((int)n);
-  size_t off = 0;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += align256(bytes); return q; };
+  const size_t nb = (size_t)blocks((long long)n, TILE);
+  Carver c{(char*)base};
   Scratch t;
-  t.keys[0] = (unsigned long long*)take(n * 8);
-  t.keys[1] = (unsigned long long*)take(n * 8);
-  t.vals[0] = (uint32_t*)take(n * 4);
-  t.vals[1] = (uint32_t*)take(n * 4);
-  t.pos = (uint32_t*)take(n * 4);
-  t.rank = (uint32_t*)take(n * 4);
-  t.hist = (uint32_t*)take((nb + 1) * 256 * 4);
+  t.keys[0] = c.take<unsigned long long>(n * 8);
+  t.keys[1] = c.take<unsigned long long>(n * 8);
+  t.vals[0] = c.take<uint32_t>(n * 4);
+  t.vals[1] = c.take<uint32_t>(n * 4);
+  t.pos = c.take<uint32_t>(n * 4);
+  t.rank = c.take<uint32_t>(n * 4);
+  t.hist = c.take<uint32_t>((nb + 1) * 256 * 4);
   if (s) *s = t;
-  return off;
+  return c.off;
 }
 
 // first position of key k in the ascending keys[0, n)
@@ -86,60 +83,21 @@ __global__ __launch_bounds__(NT) void radix_hist_kernel(Digit dg, int n, int nb,
   hist[(size_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];   // digit-major: a scan of each digit's row gives (digit, tile) bases
 }
 
-__global__ __launch_bounds__(NT) void row_scan_kernel(int nb, uint32_t* __restrict__ hist, uint32_t* __restrict__ tot) {
-  __shared__ uint32_t wt[NW];
-  uint32_t* row = hist + (size_t)blockIdx.x * nb;
-  uint32_t carry = 0;
-  for (int b0 = 0; b0 < nb; b0 += NT) {
-    const int b = b0 + threadIdx.x;
-    const uint32_t x = b < nb ? row[b] : 0u;
-    uint32_t all;
-    const uint32_t e = block_excl_scan<NW>(x, wt, all);
-    if (b < nb) row[b] = carry + e;
-    carry += all;
-  }
-  if (threadIdx.x == 0) tot[blockIdx.x] = carry;
-}
-
 // stable scatter of one tile: rounds of NT elements ranked by the ballot multi-split (element order = round, wave, lane)
 __global__ __launch_bounds__(NT) void radix_scatter_kernel(Digit dg, int n, int nb, const uint32_t* __restrict__ hist,
-                                                           const uint32_t* __restrict__ tot, const unsigned long long* __restrict__ kin,
-                                                           const uint32_t* __restrict__ vin, unsigned long long* __restrict__ kout,
-                                                           uint32_t* __restrict__ vout) {
-  __shared__ uint32_t digit_base[256];
-  __shared__ uint32_t wave_cnt[NW][256];
-  __shared__ uint32_t wt[NW];
+                                                           const unsigned long long* __restrict__ kin, const uint32_t* __restrict__ vin,
+                                                           unsigned long long* __restrict__ kout, uint32_t* __restrict__ vout) {
+  __shared__ RadixLds<NW> lds;
   const uint32_t base = blockIdx.x * (uint32_t)TILE;
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const uint32_t lane = lane_id();
-  uint32_t all;
-  digit_base[tid] = block_excl_scan<NW>(tot[tid], wt, all) + hist[(size_t)tid * nb + blockIdx.x];
+  radix_bases<NW>(lds, hist, hist + (size_t)nb * 256, nb);
   for (int r = 0; r < ITEMS; ++r) {
-    for (int w = 0; w < NW; ++w) wave_cnt[w][tid] = 0;
-    __syncthreads();
-    const uint32_t i = base + r * NT + tid;
+    radix_round_begin<NW>(lds);
+    const uint32_t i = base + r * NT + threadIdx.x;
     const bool valid = i < (uint32_t)n;
     unsigned long long k = 0; uint32_t v = 0, digit = 0;
     if (valid) { k = kin[i]; v = vin[i]; digit = dg(k); }
-    unsigned long long same = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (digit >> b) & 1u;
-      const unsigned long long m = __ballot(bit);
-      same &= bit ? m : ~m;
-    }
-    const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
-    if (valid && rank == 0) wave_cnt[wave][digit] = (uint32_t)__popcll(same);
-    __syncthreads();
-    {
-      uint32_t run = digit_base[tid];
-#pragma unroll
-      for (int w = 0; w < NW; ++w) { const uint32_t c = wave_cnt[w][tid]; wave_cnt[w][tid] = run; run += c; }
-      digit_base[tid] = run;
-    }
-    __syncthreads();
+    const uint32_t dst = radix_round_dst<NW>(lds, valid, digit);
     if (valid) {
-      const uint32_t dst = wave_cnt[wave][digit] + rank;
       kout[dst] = k;
       vout[dst] = v;
     }
@@ -149,14 +107,13 @@ __global__ __launch_bounds__(NT) void radix_scatter_kernel(Digit dg, int n, int 
 
 // sorts (keys[0], vals[0]) over `passes` bytes (or one tap pass); returns the buffer that holds the result
 int radix_sort(const Scratch& s, int n, int first_buf, int passes, int tap_k, unsigned long long limit, hipStream_t st) {
-  const int nb = n_tiles(n);
+  const int nb = blocks(n, TILE);
   int a = first_buf;
   for (int p = 0; p < passes; ++p) {
     const Digit dg{p, tap_k, limit};
     radix_hist_kernel<<<nb, NT, 0, st>>>(dg, n, nb, s.keys[a], s.hist);
-    row_scan_kernel<<<256, NT, 0, st>>>(nb, s.hist, s.hist + (size_t)nb * 256);
-    radix_scatter_kernel<<<nb, NT, 0, st>>>(dg, n, nb, s.hist, s.hist + (size_t)nb * 256, s.keys[a],
-                                            tap_k > 0 ? s.pos : s.vals[a], s.keys[a ^ 1], s.vals[a ^ 1]);
+    digit_scan_kernel<NT><<<256, NT, 0, st>>>(nb, s.hist);
+    radix_scatter_kernel<<<nb, NT, 0, st>>>(dg, n, nb, s.hist, s.keys[a], tap_k > 0 ? s.pos : s.vals[a], s.keys[a ^ 1], s.vals[a ^ 1]);
     a ^= 1;
   }
   return a;
@@ -225,70 +182,11 @@ __device__ __forceinline__ bool out_head(const unsigned long long* keys, int j, 
   return keys[j] < limit && (j == 0 || keys[j] / K != keys[j - 1] / K);
 }
 
-__global__ __launch_bounds__(NT) void head_count_kernel(int n, int K, unsigned long long limit, const unsigned long long* __restrict__ keys,
-                                                        uint32_t* __restrict__ cnt) {
-  const uint32_t base = blockIdx.x * (uint32_t)TILE;
-  uint32_t c = 0;
-  for (int r = 0; r < ITEMS; ++r) {
-    const uint32_t i = base + r * NT + threadIdx.x;
-    if (i < (uint32_t)n && out_head(keys, (int)i, K, limit)) ++c;
-  }
-  for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
-  __shared__ uint32_t part[NW];
-  if (lane_id() == 0) part[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < NW; ++w) t += part[w];
-    cnt[blockIdx.x] = t;
-  }
-}
-
-// exclusive scan of L counts in place by ONE workgroup; the total goes to *total
-__global__ __launch_bounds__(SCAN_NT) void scan_kernel(int L, uint32_t* __restrict__ v, int32_t* __restrict__ total) {
-  const int t = threadIdx.x;
-  const int ch = (L + SCAN_NT - 1) / SCAN_NT;
-  const int b = t * ch, e = min(L, b + ch);
-  uint32_t s = 0;
-  for (int i = b; i < e; ++i) s += v[i];
-  __shared__ uint32_t wt[SCAN_NT / 64];
-  const uint32_t lane = lane_id();
-  uint32_t inc = s;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = (uint32_t)__shfl_up((int)inc, o);
-    if ((int)lane >= o) inc += u;
-  }
-  if (lane == 63) wt[t >> 6] = inc;
-  __syncthreads();
-  uint32_t run = inc - s;
-  for (int w = 0; w < (t >> 6); ++w) run += wt[w];
-  for (int i = b; i < e; ++i) { const uint32_t x = v[i]; v[i] = run; run += x; }
-  if (t == SCAN_NT - 1 && total) *total = (int32_t)run;
-}
-
-// rank[j] = output row of sorted position j (heads up to and including j, minus one)
-__global__ __launch_bounds__(NT) void head_rank_kernel(int n, int K, unsigned long long limit, const unsigned long long* __restrict__ keys,
-                                                       const uint32_t* __restrict__ excl, uint32_t* __restrict__ rank) {
-  const uint32_t base = blockIdx.x * (uint32_t)TILE;
-  if (base >= (uint32_t)n) return;
-  __shared__ uint32_t wc[NW];
-  const int wave = threadIdx.x >> 6;
-  const uint32_t lane = lane_id();
-  uint32_t run = excl[blockIdx.x];
-  for (int r = 0; r < ITEMS; ++r) {
-    const uint32_t i = base + r * NT + threadIdx.x;
-    const bool valid = i < (uint32_t)n;
-    const bool f = valid && out_head(keys, (int)i, K, limit);
-    const unsigned long long m = __ballot(f);
-    if (lane == 0) wc[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t before = run, all = 0;
-    for (int w = 0; w < NW; ++w) { if (w < wave) before += wc[w]; all += wc[w]; }
-    if (valid) rank[i] = before + (uint32_t)__popcll(m & ((2ull << lane) - 1ull)) - 1u;
-    run += all;
-    __syncthreads();
-  }
-}
+struct OutHeadOp {   // rank = output row of each sorted position
+  const unsigned long long* keys; int K; unsigned long long limit; uint32_t* rank;
+  __device__ bool flag(uint32_t i) const { return out_head(keys, (int)i, K, limit); }
+  __device__ void emit(uint32_t i, uint32_t r, bool f) const { rank[i] = f ? r : r - 1u; }   // r = heads before i
+};
 
 __global__ __launch_bounds__(NT) void down_emit_kernel(int n, int K, unsigned long long limit, int O0, int O1, int O2,
                                                        const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ vals,
@@ -620,10 +518,11 @@ int u3d_spconv_down_map(int N, const int32_t* indices, int n_batch, int D0, int 
   const int K = s * s * s;
   down_key_kernel<<<blocks(N, NT), NT, 0, st>>>(N, indices, s, O[0], O[1], O[2], limit, sc.keys[0], sc.vals[0], sc.pos);
   const int fb = radix_sort(sc, N, 0, (bit_len(limit) + 7) / 8, 0, 0, st);
-  const int nb = n_tiles(N);
-  head_count_kernel<<<nb, NT, 0, st>>>(N, K, limit, sc.keys[fb], sc.hist);
-  scan_kernel<<<1, SCAN_NT, 0, st>>>(nb, sc.hist, meta);
-  head_rank_kernel<<<nb, NT, 0, st>>>(N, K, limit, sc.keys[fb], sc.hist, sc.rank);
+  const int nb = blocks(N, TILE);
+  const OutHeadOp op{sc.keys[fb], K, limit, sc.rank};
+  flag_count_kernel<NT, ITEMS, OutHeadOp><<<nb, NT, 0, st>>>(op, N, nullptr, sc.hist);
+  scan_kernel<SCAN_NT><<<1, SCAN_NT, 0, st>>>(nb, sc.hist, meta);
+  flag_apply_kernel<NT, ITEMS, OutHeadOp><<<nb, NT, 0, st>>>(op, N, nullptr, sc.hist);
   return launched();
 }
 
@@ -648,12 +547,7 @@ int u3d_spconv_down_emit(int N, int M, const int32_t* indices, int n_batch, int 
   }
   chain_kernel<<<blocks(N, NT), NT, 0, st>>>(N, limit, sc.keys[fb], sc.vals[fb], first, next);
   // one stable pass on the tap reorders the sorted positions (tap, output, row); the rows stay in vals[fb]
-  const int nb = n_tiles(N);
-  const Digit dg{0, K, limit};
-  radix_hist_kernel<<<nb, NT, 0, st>>>(dg, N, nb, sc.keys[fb], sc.hist);
-  row_scan_kernel<<<256, NT, 0, st>>>(nb, sc.hist, sc.hist + (size_t)nb * 256);
-  radix_scatter_kernel<<<nb, NT, 0, st>>>(dg, N, nb, sc.hist, sc.hist + (size_t)nb * 256, sc.keys[fb], sc.pos, sc.keys[fb ^ 1],
-                                          sc.vals[fb ^ 1]);
+  radix_sort(sc, N, fb, 1, K, limit, st);
   list_kernel<<<blocks(N, NT), NT, 0, st>>>(N, K, limit, sc.keys[fb ^ 1], sc.vals[fb ^ 1], sc.vals[fb], sc.rank, list_row, list_src);
   return launched();
 }
