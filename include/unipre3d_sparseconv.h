@@ -22,6 +22,15 @@
  *   u3d_spconv_wgrad      dW[k] = sum_o A[ia] (x) G[ig], ia = table[o,k], ig = o (gather_g == 0) or ia = o, ig = table[o,k] (gather_g == 1);
  *                         fixed-order split reduction through `partial` (u3d_spconv_wgrad_partial_floats floats).
  *   u3d_spconv_colsum     db[c] = sum_o G[o,c], fixed order through `partial` (u3d_spconv_colsum_partial_floats floats).
+ * Which kernel a shape launches (the U3D_SPCONV_* macros below; a channel count of U3D_SPCONV_SMALL_C or less is "small"):
+ *   gemm    Cin or Cout small: one VALU thread per output element; else the MFMA kernel, U3D_SPCONV_TILE rows x U3D_SPCONV_TILE
+ *           columns per block, the channels in stages of U3D_SPCONV_KSTEP; a tap with no source in a block's rows is skipped.
+ *   wgrad   Cin small: VALU, a thread per (tap, Cout channel); else Cout small: VALU, a thread per (tap, Cin channel); else MFMA,
+ *           U3D_SPCONV_TILE x U3D_SPCONV_TILE of (Cin, Cout) per block, rows in steps of U3D_SPCONV_KSTEP (a step with no source at
+ *           the tap is skipped).  Rows are divided over u3d_spconv_wgrad_partial_floats / (K * Cin * Cout) splits of equal length,
+ *           a multiple of U3D_SPCONV_KSTEP, so trailing splits may own no row; a split's partial is then 0.
+ *   colsum  u3d_spconv_colsum_partial_floats / C splits of rows.
+ *   Partials are added per output by one thread in split order, or, from U3D_SPCONV_WAVE_SUM_SPLITS splits on, by one wave.
  * scratch: u3d_spconv_scratch_bytes(N) bytes, shared by a map call and its emit.
  * Returns 0 ok, 1 invalid argument, 2 unsupported shape, 3 launch failure.
  */
@@ -33,6 +42,10 @@
 extern "C" {
 #endif
 #define U3D_SPCONV_ABI_VERSION 1
+#define U3D_SPCONV_SMALL_C 8           /* a channel count at or below this takes the VALU kernels */
+#define U3D_SPCONV_TILE 64             /* rows and columns of an MFMA block tile */
+#define U3D_SPCONV_KSTEP 32            /* reduction elements per LDS stage; rows per wgrad step */
+#define U3D_SPCONV_WAVE_SUM_SPLITS 64  /* from this many splits on, a wave adds an output's partials */
 int u3d_spconv_abi_version(void);
 size_t u3d_spconv_scratch_bytes(int n);
 int u3d_spconv_subm_map(int N, const int32_t* indices, int n_batch, int D0, int D1, int D2, int k, int32_t* table, int32_t* first,

@@ -159,3 +159,128 @@ def test_chains_np_against_dictionaries():
         assert all(first[r] == rs[0] for r in rs)
         assert [int(nxt[r]) for r in rs] == rs[1:] + [-1]
     assert R.chains_np(np.zeros((0, 4), np.int64), (4, 4, 4))[0].shape == (0,)
+
+
+# ---- tests/spconv_kernel_ref.py: the C-ABI contractions and the structured tables ------------------------------------------------------------
+import spconv_kernel_ref as KR
+
+
+def _ints(g, *shape):
+    return torch.as_tensor(g.integers(-4, 5, size=shape)).double()
+
+
+def test_kernel_references_agree_with_scalar_loops():
+    """gemm (table mode, list mode, mask, out_rows), wgrad (both sides), colsum and dupsum against the header's sentences as Python loops"""
+    g = np.random.default_rng(0)
+    R, K, Cin, Cout, Ra = 5, 3, 2, 3, 4
+    A, W, b = _ints(g, Ra, Cin), _ints(g, K, Cin, Cout), _ints(g, Cout)
+    T = g.integers(-1, Ra, size=(R, K))
+    mask = np.array([0, 0, 2, 1, 4])
+    for bias in (None, b):
+        for m in (None, mask):
+            want = torch.zeros(R, Cout, dtype=torch.float64)
+            for o in range(R):
+                for n in range(Cout):
+                    s = 0.0 if bias is None else float(bias[n])
+                    for k in range(K):
+                        if T[o, k] >= 0:
+                            for c in range(Cin):
+                                s += float(A[T[o, k], c]) * float(W[k, c, n])
+                    want[o, n] = 0.0 if (m is not None and m[o] != o) else s
+            assert torch.equal(KR.gemm_ref(A, W, bias, T, mask=m), want)
+    # list mode: 6 entries into 7 output rows, one entry dropped
+    list_row, list_src = np.array([5, 0, 6, 2, 1, 3]), np.array([1 * K + 2, -1, 3 * K + 0, 0 * K + 1, 3 * K + 2, 2 * K + 0])
+    mask7 = np.array([0, 1, 0, 3, 4, 5, 2])
+    for bias in (None, b):
+        for m in (None, mask7):
+            want = torch.zeros(7, Cout, dtype=torch.float64)
+            for e in range(6):
+                o = list_row[e]
+                row = torch.zeros(Cout, dtype=torch.float64) if bias is None else bias.clone()
+                if list_src[e] >= 0:
+                    row = row + A[list_src[e] // K] @ W[list_src[e] % K]
+                want[o] = 0 if (m is not None and m[o] != o) else row
+            got = KR.gemm_ref(A, W, bias, list_src, list_row=list_row, mask=m, out_rows=7)
+            assert torch.equal(got, want) and not got[4].any()          # row 4: no entry writes it
+    # wgrad: the gathered side holds Ra rows, the other side R
+    for gather_g in (0, 1):
+        Aw, Gw = (_ints(g, R, Cin), _ints(g, Ra, Cout)) if gather_g else (_ints(g, Ra, Cin), _ints(g, R, Cout))
+        want = torch.zeros(K, Cin, Cout, dtype=torch.float64)
+        for k in range(K):
+            for o in range(R):
+                if T[o, k] >= 0:
+                    ia, ig = (o, T[o, k]) if gather_g else (T[o, k], o)
+                    for c in range(Cin):
+                        for n in range(Cout):
+                            want[k, c, n] += float(Aw[ia, c]) * float(Gw[ig, n])
+        assert torch.equal(KR.wgrad_ref(Aw, Gw, T, gather_g), want)
+    G = _ints(g, 7, 3)
+    assert torch.equal(KR.colsum_ref(G), torch.stack([sum(G[o, c] for o in range(7)) for c in range(3)]))
+    first, nxt = np.array([0, 1, 0, 5, 1, 5, 0]), np.array([2, 4, 6, -1, -1, 3, -1])   # chains 0-2-6, 1-4, 5-3 (descending)
+    want = torch.zeros(7, 3, dtype=torch.float64)
+    for r in range(7):
+        if first[r] == r:
+            j = r
+            while j >= 0:
+                want[r] += G[j]
+                j = nxt[j]
+    assert torch.equal(KR.dupsum_ref(G, first, nxt), want) and not want[[2, 3, 4, 6]].any() and want[5].equal(G[5] + G[3])
+
+
+@pytest.mark.parametrize("per", [32, 64])
+@pytest.mark.parametrize("R,K", [(1, 1), (63, 8), (64, 27), (65, 8), (129, 27), (300, 8)])
+def test_structured_tables_hold_what_they_claim(R, K, per):
+    for pattern in sorted(set(KR.GEMM_PATTERNS + KR.WGRAD_PATTERNS)):
+        for n_src in (R, R + 7, max(1, R // 2)):
+            T, claim = KR.build_table(pattern, R, K, n_src, per, seed=R + K)
+            assert T.dtype == np.int32 and T.shape == (R, K) and T.min() >= -1 and T.max() < n_src, pattern
+            assert KR.live_rows(T) == claim["live_rows"], pattern
+            assert np.array_equal(KR.block_tap_live(T, per), claim["cells"]), pattern
+    nb = -(-R // per)
+    T, c = KR.build_table("empty", R, K, R, per)
+    assert (T == -1).all() and not c["cells"].any()
+    T, c = KR.build_table("block_last_row", R, K, R, per)
+    assert c["live_rows"] == [min((j + 1) * per, R) - 1 for j in range(nb)] and all((T[r] >= 0).all() for r in c["live_rows"])
+    T, c = KR.build_table("block_tap", R, K, R, per)
+    assert all(list(np.nonzero(c["cells"][j])[0]) == [j % K] for j in range(nb))
+    T, c = KR.build_table("one_source", R, K, R + 7, per)
+    assert len(np.unique(T)) == 1 and T[0, 0] >= 0
+    T, c = KR.build_table("step_last_row", R, K, R, per)
+    assert c["live_rows"] == [o for o in range(R) if o % per == per - 1]
+    T, c = KR.build_table("empty_steps", R, K, R, per)
+    assert [bool(c["cells"][j].all()) for j in range(nb)] == [j % 3 == 0 for j in range(nb)] and not c["cells"][1::3].any()
+    T, c = KR.build_table("empty_tap", R, K, R, per)
+    assert (T[:, K // 2] == -1).all() and not c["cells"][:, K // 2].any()
+    T, c = KR.build_table("last_row_only", R, K, R, per)
+    assert c["live_rows"] == [R - 1] and (T[R - 1] >= 0).all() and int(c["cells"].sum()) == K
+    T, c = KR.build_table("sparse", 300, 27, 300, per)
+    assert 0.10 < (T >= 0).mean() < 0.20
+
+
+@pytest.mark.parametrize("R,K,n_src", [(1, 1, 1), (65, 8, 40), (129, 27, 200)])
+def test_structured_lists_masks_and_chains_hold_what_they_claim(R, K, n_src):
+    for pattern in KR.LIST_PATTERNS:
+        row, src, claim = KR.build_list(pattern, R, K, n_src, seed=R)
+        assert row.dtype == src.dtype == np.int32 and sorted(row.tolist()) == list(range(R)) and src.min() >= -1 and src.max() < n_src * K
+        assert sorted(int(o) for o, s in zip(row, src) if s >= 0) == claim["live_outputs"]
+        taps = [int(s % K) for s in src if s >= 0]
+        assert sorted(set(taps)) == claim["taps"]
+        if pattern == "empty":
+            assert (src == -1).all()
+        if pattern == "one_tap":
+            assert set(taps) <= {K - 1}
+        if pattern in ("tap_major", "one_tap"):
+            assert taps == sorted(taps) and (src[len(taps):] == -1).all()
+    if R > 64:
+        taps = [int(s % K) for s in KR.build_list("shuffled", R, K, n_src, seed=R)[1] if s >= 0]
+        assert taps != sorted(taps)
+    mask, kept = KR.build_mask(R, seed=K)
+    assert kept == [o for o in range(R) if mask[o] == o] and 0 in kept and all(0 <= mask[o] < o for o in range(R) if o not in kept)
+    if R > 64:
+        assert 0.4 * R < len(kept) < 0.8 * R and (mask[1:] == 0).any()
+        for order in ("ascending", "descending"):
+            first, nxt, chains = KR.build_chains(R, [1, 2, 40], order, seed=K)
+            assert sorted(r for c in chains for r in c) == list(range(R)) and [len(c) for c in chains[:3]] == [1, 2, 40]
+            for c in chains:
+                assert all(first[r] == c[0] for r in c) and [int(nxt[r]) for r in c] == c[1:] + [-1]
+                assert c == sorted(c, reverse=order == "descending")

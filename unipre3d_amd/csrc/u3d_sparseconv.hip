@@ -18,8 +18,10 @@ constexpr int NW = NT / 64;
 constexpr int ITEMS = 16;            // rounds of NT elements per tile of the sort and scan passes
 constexpr int TILE = NT * ITEMS;
 constexpr int SCAN_NT = 1024;        // the one-workgroup exclusive scan
-constexpr int BM = 64, BN = 64, BK = 32;   // GEMM block tile: 64 rows x 64 columns, 32 of the reduction per LDS stage
-constexpr int SMALL_C = 8;           // a channel count at or below this takes the VALU kernels (the stem's Cin = 3 / 6)
+// the class boundaries are public (unipre3d_sparseconv.h): the tests place their shapes on both sides of each
+constexpr int BM = U3D_SPCONV_TILE, BN = U3D_SPCONV_TILE, BK = U3D_SPCONV_KSTEP;   // GEMM block tile: 64 rows x 64 columns, 32 of the reduction per LDS stage
+constexpr int SMALL_C = U3D_SPCONV_SMALL_C;   // a channel count at or below this takes the VALU kernels (the stem's Cin = 3 / 6)
+constexpr int WAVE_SUM_SPLITS = U3D_SPCONV_WAVE_SUM_SPLITS;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -440,7 +442,7 @@ __global__ __launch_bounds__(NT) void split_sum_wave_kernel(long long n, int spl
 }
 
 void split_sum(long long n, int splits, const float* part, float* out, hipStream_t st) {
-  if (splits >= 64) split_sum_wave_kernel<<<blocks(n * 64, NT), NT, 0, st>>>(n, splits, part, out);
+  if (splits >= WAVE_SUM_SPLITS) split_sum_wave_kernel<<<blocks(n * 64, NT), NT, 0, st>>>(n, splits, part, out);
   else split_sum_kernel<<<blocks(n, NT), NT, 0, st>>>(n, splits, part, out);
 }
 
