@@ -1,6 +1,7 @@
 /*
  * unipre3d_offsetops.h -- C-ABI of the MI355X (gfx950) offset-batched ("ragged") point operators: the counterpart of
- * openpoints/cpp/pointops (knnquery, ballquery, grouping, interpolation, subtraction, aggregation; not furthestsampling) and of the
+ * openpoints/cpp/pointops (knnquery, ballquery, grouping, interpolation, subtraction, aggregation; furthestsampling is u3d_offset_furthest_sampling of
+ * unipre3d_pointops.h, beside the dense furthest point sampling whose tie keys and contraction modes it shares) and of the
  * `pointops.knn_query` call of pointcept/engines/hooks/evaluator.py.  Semantics restated on the CPU in tests/offsetops_ref.py.
  *
  * Conventions (as unipre3d_knn.h): raw DEVICE pointers and a HIP stream; fp32 data, int32 indices, int32 offsets; contiguous

@@ -5,7 +5,7 @@
  * which the transformer / pointmlp backbones and the ShapeNet loader need before anything can feed the render-loss path
  * (openpoints/models/layers/subsample.py:77-107, group.py:76-203; dataset/shapenet.py:368).  Each function takes the
  * reference wrapper's integer arguments in the same order, raw DEVICE pointers instead of at::Tensor, and a HIP stream.
- * fp32 data, int32 indices, contiguous row-major.  Returns 0 on success, 1 invalid argument, 3 launch failure.
+ * fp32 data, int32 indices, contiguous row-major.  Returns 0 on success, 1 invalid argument, 3 launch failure (2: over the grid form's capacity, below).
  *
  *   u3d_furthest_point_sampling  <- furthest_point_sampling_wrapper(b, n, m, points (B,N,3), temp (B,N), idx (B,M))
  *        Start index 0; ties in the arg-max resolve exactly as the reference's block reduction does for its block size
@@ -26,9 +26,29 @@
  *   u3d_three_interpolate_grad   <- three_interpolate_grad_wrapper(b, c, n, m, grad_out (B,C,N), idx, weight, grad_points (B,C,M))
  *        (:23, interpolate_gpu.cu:127-148) ACCUMULATES grad_out * weight into grad_points with float atomics; zero it first
  *        (openpoints/models/layers/upsampling.py:86).
+ *
+ * Furthest point sampling over a grid of workgroups (csrc/u3d_fps_grid.h; DESIGN.md, "Furthest point sampling over a grid of workgroups"):
+ * one cloud is cut into slices of P = u3d_fps_grid_points_per_workgroup() rows, one workgroup per slice, which meet once per selection.
+ *   u3d_furthest_point_sampling_grid(b, n, m, points (B,N,3), workspace, idx (B,M), stream)
+ *        The same selection as u3d_furthest_point_sampling, bit for bit, in every contraction mode, for clouds of any size.
+ *   u3d_offset_furthest_sampling(b, n, m, xyz (n,3), offset (b), new_offset (b), workspace, idx (m), stream)
+ *        <- furthestsampling_cuda (openpoints/cpp/pointops/src/sampling/sampling_cuda_kernel.cu; functions/pointops.py:10-29) for a
+ *        concatenated batch: segment s = rows [offset[s-1], offset[s]) (0 for s = 0; clamped to [0, n]; end < start is empty) writes
+ *        idx[new_offset[s-1] .. new_offset[s]) (clamped to [0, m]) with ABSOLUTE rows.  Its first selection is its first row, running
+ *        minima start at 1e10f, d2 = (x2-x1)^2 + (y2-y1)^2 + (z2-z1)^2 in the contraction mode, and equal distances resolve as the
+ *        reference's block does for the block size opt_n_threads(n_max) of the LARGEST segment (computed on the device).  A segment
+ *        asked for more selections than it has rows simply goes on (all minima 0, the tie order decides).  Departures: a segment asked
+ *        for nothing writes nothing; an EMPTY segment asked for selections gets -1; idx beyond new_offset[b-1] is not written.
+ * Both take a caller-provided DEVICE workspace of u3d_fps_grid_workspace_bytes(b) bytes, which the library clears on the stream before
+ * the launch; its first 32-bit word is a status word: 0 after a sound call, non-zero when a wait inside the kernel gave up (2 s), in
+ * which case the unfinished segments' remaining outputs are -1.  The grid is at most 256 workgroups, so the capacity is
+ * rows <= (256 - b) * P (rows = b * n for the dense form): beyond it the call returns 2 and launches nothing.  Only one such grid is in
+ * flight per device: the library chains the launches with an event (the one state that outlives a call); under stream capture the
+ * calls return 1.
  */
 #ifndef UNIPRE3D_POINTOPS_H
 #define UNIPRE3D_POINTOPS_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -55,6 +75,11 @@ int u3d_pointops_set_contraction(int mode); /* 0 ok, 1 unknown mode; applies to 
 int u3d_pointops_get_contraction(void);
 
 int u3d_furthest_point_sampling(int b, int n, int m, const float* points, float* temp, int32_t* idx, void* stream);
+size_t u3d_fps_grid_workspace_bytes(int b);
+int u3d_fps_grid_points_per_workgroup(void); /* P, for callers and tests */
+int u3d_furthest_point_sampling_grid(int b, int n, int m, const float* points, void* workspace, int32_t* idx, void* stream);
+int u3d_offset_furthest_sampling(int b, int n, int m, const float* xyz, const int32_t* offset, const int32_t* new_offset,
+                                 void* workspace, int32_t* idx, void* stream);
 int u3d_ball_query(int b, int n, int m, float radius, int nsample, const float* new_xyz, const float* xyz, int32_t* idx,
                    void* stream);
 int u3d_group_points(int b, int c, int n, int npoints, int nsample, const float* points, const int32_t* idx, float* out,

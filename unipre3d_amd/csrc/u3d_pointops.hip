@@ -13,6 +13,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <mutex>
+
 #include "unipre3d_pointops.h"
 #include "u3d_util.h"
 
@@ -295,6 +297,8 @@ __global__ __launch_bounds__(1024) void fps_kernel_large(int n, int m, int lg, c
     if (tid == 0) out[j] = old;
   }
 }
+
+#include "u3d_fps_grid.h"   // fps_grid_kernel: one cloud over several workgroups
 
 template <int CM>
 __global__ __launch_bounds__(256) void ball_query_kernel(int n, int m, int total_q, float radius2, int nsample,
@@ -720,9 +724,68 @@ inline int interp_grad_rows(int b, int c, int m) { return m > 0 ? grad_rows(m, b
     else hipLaunchKernelGGL((KERNEL<U3D_PO_NO_FMA>), __VA_ARGS__);                                    \
   } while (0)
 
+// Host side of the grid kernel (u3d_fps_grid.h).  Two grids that each want most of the CUs could hold half of them each and wait for the other
+// half for ever (until the bounded waits give up), so only ONE grid is in flight per device: an event recorded after every grid launch, which the
+// next grid launch's stream waits on first -- the only state that outlives a call.  The workspace clear rides on the call's stream behind that wait.
+struct FgDevice { hipEvent_t done = nullptr; int cus = 0; };
+std::mutex g_fg_mutex;
+FgDevice g_fg_device[64];
+
+int fps_grid_launch(int b, int n, int m, int dense, int lg, const float* xyz, const int32_t* offset, const int32_t* new_offset, void* workspace,
+                    int32_t* idx, hipStream_t s) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 3;
+  std::lock_guard<std::mutex> lock(g_fg_mutex);
+  FgDevice& d = g_fg_device[dev];
+  if (d.cus == 0) {
+    if (hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || d.cus <= 0) { d.cus = 0; return 3; }
+  }
+  // one workgroup per CU, never more than FG_MAX_WG: every slice of every segment is resident whatever order the workgroups start in
+  const long long cap = d.cus < FG_MAX_WG ? d.cus : FG_MAX_WG;
+  const long long rows = dense ? (long long)b * n : (long long)n;
+  if (b >= cap || rows > (cap - b) * FG_P) return 2;
+  const long long want = (rows + FG_P - 1) / FG_P + b;
+  const int grid = (int)(want < cap ? want : cap);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {   // the event chain cannot be captured
+    (void)hipGetLastError();
+    return 1;
+  }
+  if (!d.done) {
+    if (hipEventCreateWithFlags(&d.done, hipEventDisableTiming) != hipSuccess) { d.done = nullptr; return 3; }
+  } else if (hipStreamWaitEvent(s, d.done, 0) != hipSuccess) {
+    return 3;
+  }
+  if (hipMemsetAsync(workspace, 0, fg_workspace_bytes(b), s) != hipSuccess) return 3;
+  U3D_PO_LAUNCH_CM(fps_grid_kernel, dim3(grid), dim3(FG_THREADS), 0, s, b, n, m, dense, lg, xyz, offset, new_offset, (unsigned char*)workspace, idx);
+  const int rc = launched();
+  if (hipEventRecord(d.done, s) != hipSuccess) return 3;
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t u3d_fps_grid_workspace_bytes(int b) { return fg_workspace_bytes(b); }
+int u3d_fps_grid_points_per_workgroup(void) { return FG_P; }
+
+int u3d_furthest_point_sampling_grid(int b, int n, int m, const float* points, void* workspace, int32_t* idx, void* stream) {
+  if (b < 0 || n < 0 || m < 0) return 1;
+  if (b == 0 || m == 0) return 0;
+  if (n <= 0 || !points || !idx || !workspace) return 1;
+  const int pow_2 = (int)(log((double)n) / log(2.0));   // opt_n_threads(n), as u3d_furthest_point_sampling evaluates it
+  const int lg = pow_2 > 10 ? 10 : (pow_2 < 0 ? 0 : pow_2);
+  return fps_grid_launch(b, n, m, 1, lg, points, nullptr, nullptr, workspace, idx, (hipStream_t)stream);
+}
+
+int u3d_offset_furthest_sampling(int b, int n, int m, const float* xyz, const int32_t* offset, const int32_t* new_offset, void* workspace,
+                                 int32_t* idx, void* stream) {
+  if (b < 0 || n < 0 || m < 0) return 1;
+  if (b == 0 || m == 0) return 0;
+  if ((n > 0 && !xyz) || !offset || !new_offset || !idx || !workspace) return 1;
+  return fps_grid_launch(b, n, m, 0, 0, xyz, offset, new_offset, workspace, idx, (hipStream_t)stream);
+}
 
 int u3d_furthest_point_sampling(int b, int n, int m, const float* points, float* temp, int32_t* idx, void* stream) {
   if (b < 0 || n < 0 || m < 0) return 1;

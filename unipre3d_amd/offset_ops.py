@@ -9,6 +9,8 @@ Offsets are int32 or int64 DEVICE tensors; nothing here reads them on the host (
                    pointcept/engines/hooks/evaluator.py:125-132 (`import unipre3d_amd.offset_ops as pointops`)
   knn_query_raw    the thin core -> (dist2, idx)
   ballquery        (radius, nsample, xyz, new_xyz, offset, new_offset) -> idx int32 (m,nsample)
+  furthestsampling (xyz, offset, new_offset, m=None) -> idx int32 (m,): furthest point sampling per segment, absolute rows
+                   (libunipre3d_pointops.so: u3d_offset_furthest_sampling, include/unipre3d_pointops.h)
   grouping, subtraction, aggregation, interpolation2      autograd Functions (fp32 kernels, first-order gradients)
   interpolation, querygroup, queryandgroup                compositions, as the reference writes them
 
@@ -34,7 +36,11 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
+from . import pointops as _pointops
 from ._lib import check, on_device, stream_ptr
+
+__all__ = ["knn_query_raw", "knnquery", "knn_query", "ballquery", "furthestsampling", "grouping", "subtraction", "aggregation",
+           "interpolation2", "interpolation", "querygroup", "queryandgroup"]
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_offsetops.so")
 MAX_K = 64                                                    # include/unipre3d_knn.h: U3D_KNN_MAX_K
@@ -130,6 +136,39 @@ def ballquery(radius, nsample, xyz, new_xyz, offset, new_offset):
         return torch.zeros(m, ns, dtype=torch.int32, device=dev)
     idx = torch.empty(m, ns, dtype=torch.int32, device=dev)
     _call("u3d_offset_ballquery", b, n, m, float(radius), ns, _p(xyz), _p(new_xyz), _p(offset), _p(new_offset), _p(idx), stream_ptr(dev))
+    return idx
+
+
+@torch.no_grad()
+def furthestsampling(xyz, offset, new_offset, m=None):
+    """pointops.py `furthestsampling`: xyz (n,3), offset (b), new_offset (b) -> idx int32 (m,): segment s contributes its
+    new_offset[s] - new_offset[s-1] furthest-point-sampled rows, as ABSOLUTE rows of xyz, starting from its first row; equal distances
+    resolve as the reference's block does for its largest segment.  m defaults to int(new_offset[-1]) -- the reference's one host
+    sync; pass it to avoid the sync.  A segment asked for nothing writes nothing, an empty segment asked for rows gets -1 (SURVEY.md,
+    defect appendix); any other -1 means the kernel's status word was set (unipre3d_amd.pointops.grid_status).  No autograd: indices.
+    A batch beyond the grid's capacity of (256 - b) * 4096 rows raises."""
+    if xyz.dim() != 2:
+        raise ValueError(f"xyz (n,3) expected, got {tuple(xyz.shape)}")
+    if xyz.size(1) != 3:
+        raise NotImplementedError(f"furthest point sampling is built for 3 coordinates, got {xyz.size(1)}")
+    if offset.dim() != 1 or new_offset.dim() != 1 or offset.numel() != new_offset.numel():
+        raise ValueError(f"offset (b) and new_offset (b) expected, got {tuple(offset.shape)} and {tuple(new_offset.shape)}")
+    dev = on_device("offset_ops", xyz, offset, new_offset)
+    xyz, offset, new_offset = _f32(xyz, "xyz"), _i32(offset, "offset"), _i32(new_offset, "new_offset")
+    n, b = xyz.size(0), offset.numel()
+    if m is None:
+        m = int(new_offset[-1]) if b else 0
+    m = int(m)
+    if m < 0:
+        raise ValueError(f"m = {m} is negative")
+    idx = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    if b == 0 or m == 0:
+        return idx
+    rc = _pointops.load().u3d_offset_furthest_sampling(b, n, m, _p(xyz), _p(offset), _p(new_offset), _p(_pointops.grid_workspace(b, dev)),
+                                                       _p(idx), stream_ptr(dev))
+    if rc == _pointops.STATUS_OVER_CAPACITY:
+        raise RuntimeError(f"furthestsampling: {n} rows in {b} segments are beyond the grid kernel's capacity")
+    check(rc, "u3d_offset_furthest_sampling", named=False)
     return idx
 
 

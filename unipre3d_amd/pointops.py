@@ -31,6 +31,10 @@ def set_contraction(mode: str) -> None:
 _i, _f, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 SIGNATURES = {   # include/unipre3d_pointops.h
     "u3d_furthest_point_sampling": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_fps_grid_workspace_bytes": (ctypes.c_size_t, [_i]),
+    "u3d_fps_grid_points_per_workgroup": (_i, []),
+    "u3d_furthest_point_sampling_grid": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_offset_furthest_sampling": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "u3d_ball_query": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
     "u3d_group_points": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "u3d_group_points_grad": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -71,6 +75,33 @@ def _i32(idx, what):
     raise TypeError(f"{what} must be an int32 (or int64) index tensor, got {idx.dtype}")
 
 
+# Clouds above N_GRID points are sampled by the grid kernel (one cloud over several workgroups, csrc/u3d_fps_grid.h); at or below it, and
+# beyond the grid's capacity, by the one-workgroup-per-cloud kernels.  From tools/fps_bench.py's table (profiles/fps/): the grid
+# kernel is ahead at every measured shape from 16 384 points up (2.4 x there, 7.8 x and 12 x at the loader's); nothing was measured between
+# 8192 and 16 384, so those clouds keep their path.  Never below 8192.
+N_GRID = 16383
+STATUS_OVER_CAPACITY = 2                                       # include/unipre3d_pointops.h
+
+_grid_ws = {}
+
+
+def grid_workspace(b: int, dev) -> torch.Tensor:
+    """The device's workspace of the grid kernel for b segments: slots, counters and the status word (a few hundred bytes).  One tensor
+    per device is kept and reused on every stream: the library clears it on the call's stream behind its one-grid-in-flight wait."""
+    need = int(load().u3d_fps_grid_workspace_bytes(int(b)))
+    ws = _grid_ws.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = _grid_ws[dev] = torch.zeros(max(need, 4096), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def grid_status(dev) -> int:
+    """The status word the device's last grid call left (0: sound; non-zero: a wait inside the kernel gave up and -1 was written).
+    Synchronises."""
+    ws = _grid_ws.get(dev)
+    return 0 if ws is None else int(ws[:4].view(torch.int32).item())
+
+
 class FurthestPointSampling(Function):
     @staticmethod
     def forward(ctx, xyz: torch.Tensor, npoint: int) -> torch.Tensor:
@@ -80,6 +111,12 @@ class FurthestPointSampling(Function):
         xyz = _f32(xyz, "xyz")
         B, N, _ = xyz.size()
         out = torch.empty(B, npoint, dtype=torch.int32, device=xyz.device)
+        if N > N_GRID and B > 0 and npoint > 0:
+            rc = load().u3d_furthest_point_sampling_grid(B, N, npoint, _lib.ptr(xyz), _lib.ptr(grid_workspace(B, xyz.device)), _lib.ptr(out),
+                                                         stream_ptr(dev))
+            if rc != STATUS_OVER_CAPACITY:
+                check(rc, "fps (grid)", named=False)
+                return out
         temp = torch.empty(B, N, dtype=torch.float32, device=xyz.device) if N > 8192 else None
         check(load().u3d_furthest_point_sampling(B, N, npoint, _lib.ptr(xyz), _lib.ptr(temp), _lib.ptr(out), stream_ptr(dev)), "fps", named=False)
         return out
