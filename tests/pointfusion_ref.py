@@ -13,10 +13,16 @@ FNV_PRIME = np.uint64(0x100000001B3)
 
 
 def grid_coords(coord, min_coord, grid_size=0.02, fp64=False):
+    """The reference's two origins: an explicit min_coord gives floor((coord - min_coord) / gs); min_coord=None gives
+    g = floor(coord / gs), grid = g - g.min(0) (the cells are those of the absolute grid, NOT the ones anchored at coord.min(0))."""
     coord = np.asarray(coord, np.float32)
-    d = coord - np.asarray(min_coord, np.float32).reshape(1, 3)
+    d = coord if min_coord is None else coord - np.asarray(min_coord, np.float32).reshape(1, 3)
     q = d.astype(np.float64) / np.float64(grid_size) if fp64 else d / np.float32(grid_size)
-    return np.floor(q).astype(np.int64)
+    with np.errstate(invalid="ignore"):     # out of int64's range: the x86 conversion, INT64_MIN
+        g = np.floor(q).astype(np.int64)
+    if min_coord is None and len(g):
+        g -= g.min(0)
+    return g
 
 
 def fnv_keys(grid):
@@ -31,7 +37,8 @@ def fnv_keys(grid):
 
 
 def voxelize(coord, min_coord, grid_size=0.02):
-    """-> dict grid (N,3), key (N,), order (N,) stable argsort of the keys, count / start (M,), inverse (N,)."""
+    """min_coord: (3,) or None (the default origin of grid_coords).
+    -> dict grid (N,3), key (N,), order (N,) stable argsort of the keys, count / start (M,), inverse (N,)."""
     grid = grid_coords(coord, min_coord, grid_size)
     key = fnv_keys(grid)
     order = np.argsort(key, kind="stable")
@@ -53,8 +60,6 @@ def pick(vox, draws=None, mode="train", part=0):
 
 def grid_sample(coord, min_coord=None, grid_size=0.02, draws=None, mode="train", part=0):
     coord = np.asarray(coord, np.float32)
-    if min_coord is None:
-        min_coord = coord.min(0)
     vox = voxelize(coord, min_coord, grid_size)
     idx = pick(vox, draws, mode, part)
     return {"index": idx, "coord": coord[idx], "grid_coord": vox["grid"][idx], "inverse": vox["inverse"], "count": vox["count"],

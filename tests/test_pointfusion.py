@@ -1,6 +1,7 @@
 """Scene-level PointFusion, host side: the numpy restatement tests/pointfusion_ref.py against golden vectors produced by
 the reference's OWN fusion/point_fusion.py + pointcept GridSample (tests/golden/g11_point_fusion.npz, make_g11_point_fusion.py), the
-fp32-division pin, and the C-ABI of libunipre3d_pointfusion.so (loads without a GPU; no compute calls here)."""
+fp32-division pin, pointcept's GridSample on its own with both origins (tests/golden/g17_grid_sample.npz, make_g17_grid_sample.py),
+and the C-ABI of libunipre3d_pointfusion.so (loads without a GPU; no compute calls here)."""
 import ctypes
 import os
 import re
@@ -94,6 +95,86 @@ def test_fnv_is_multiply_then_xor():
     assert int(R.fnv_keys(g)[1]) != 0xCBF29CE484222325
 
 
+# ---- GridSample on its own: both origins, both modes (G17) -----------------------------------------------------------------------
+G17_DEF = ("shift", "neg", "straddle", "boundary", "fp64", "one", "onevoxel")
+G17_EXP = G17_DEF + ("range",)
+
+
+@pytest.fixture(scope="module")
+def g17(golden):
+    g = golden("g17_grid_sample.npz")
+    assert tuple(g["names_def"]) == G17_DEF and tuple(g["names"]) == G17_EXP
+    return g
+
+
+def _g17_restatement_equals_the_record(g, name, origin):
+    coord, gs = g[f"{name}_coord"], g[f"{name}_grid_size"]
+    mn = None if origin == "def" else g[f"{name}_min_coord"]
+    rec = lambda k: g[f"{name}_{origin}_{k}"]
+    tr = R.grid_sample(coord, mn, gs, draws=rec("draws"))
+    assert len(rec("draws")) == len(tr["count"]) and rec("draws").max() < tr["count"].max()
+    assert np.array_equal(tr["index"], rec("train_index"))
+    assert np.array_equal(tr["grid_coord"], rec("train_grid_coord"))
+    assert np.array_equal(tr["inverse"], rec("train_inverse"))
+    assert len(rec("test_index")) == tr["count"].max()          # one part per i < count.max()
+    for part, (idx, grid) in enumerate(zip(rec("test_index"), rec("test_grid_coord"))):
+        te = R.grid_sample(coord, mn, gs, mode="test", part=part)
+        assert np.array_equal(te["index"], idx), part
+        assert np.array_equal(te["grid_coord"], grid), part
+        assert np.array_equal(te["inverse"], rec("test_inverse"))
+
+
+@pytest.mark.parametrize("name", G17_DEF)
+def test_restatement_reproduces_grid_sample_default_origin(g17, name):
+    """min_coord=None: g = floor(coord / gs), grid = g - g.min(0); every recorded output of the reference's class, bit for bit."""
+    _g17_restatement_equals_the_record(g17, name, "def")
+
+
+@pytest.mark.parametrize("name", G17_EXP)
+def test_restatement_reproduces_grid_sample_explicit_origin(g17, name):
+    """min_coord given: grid = floor((coord - min_coord) / gs); `range` holds the coordinates at and beyond int64's ends."""
+    _g17_restatement_equals_the_record(g17, name, "exp")
+
+
+def test_g17_reaches_where_origins_and_precisions_part(g17):
+    """The fixture's clouds do what they are there for (else the tests above could pass on a wrong origin or precision)."""
+    gs = np.float32(0.02)
+    for name in ("shift", "neg", "boundary"):        # anchoring the cells at coord.min(0) gives other voxels than the default origin
+        c = g17[f"{name}_coord"]
+        assert len(R.voxelize(c, c.min(0), gs)["count"]) != len(g17[f"{name}_def_draws"]), name
+    c = g17["straddle_coord"]
+    assert np.all(c.min(0) < 0) and np.all(c.max(0) > 0) and np.all(g17["neg_coord"] < 0)
+    c, m = g17["boundary_coord"], g17["boundary_min_coord"]
+    k = np.arange(-40, 40)
+    on_abs = np.isin(c, (k * gs).astype(np.float32)).all(1)
+    on_min = np.stack([np.isin(c[:, a], (m[a] + (k * gs).astype(np.float32)).astype(np.float32)) for a in range(3)], 1).all(1)
+    assert on_abs.sum() >= 100 and on_min.sum() >= 100
+    c, m = g17["fp64_coord"], g17["fp64_min_coord"]
+    rd, re = g17["fp64_def_rows"], g17["fp64_exp_rows"]
+    assert len(rd) >= 4 and len(re) >= 4
+    assert np.all(np.floor(c[rd, 0] / gs) != np.floor(c[rd, 0].astype(np.float64) / 0.02))
+    assert np.all(R.grid_coords(c[re], m, gs)[:, 1] != R.grid_coords(c[re], m, 0.02, fp64=True)[:, 1])
+    assert len(g17["one_coord"]) == 1 and len(g17["onevoxel_def_draws"]) == len(g17["onevoxel_exp_draws"]) == 1
+    c = g17["range_coord"]
+    big = np.float32(2.0 ** 63 - 2.0 ** 39)
+    for v in (np.inf, -np.inf, np.float32(3e30), big, -big, np.float32(2.0 ** 63), np.float32(-2.0 ** 63)):
+        assert (c == v).any(), v
+    assert not np.isnan(c).any()
+    grid = g17["range_exp_train_grid_coord"]                 # numpy on x86: exact where the floor fits int64, INT64_MIN elsewhere
+    assert (grid == 2 ** 63 - 2 ** 39).any() and (grid == -(2 ** 63 - 2 ** 39)).any() and (grid == -2 ** 63).any()
+
+
+@pytest.mark.parametrize("name", G17_DEF)
+def test_minimum_of_the_floors_is_the_floor_of_the_minimum(g17, name):
+    """What the kernel's default origin rests on: floor and the fp32 division by a positive grid size are monotone, so (without NaN)
+    g.min(0) == floor(fp32(coord.min(0) / gs)) and the per-set minimum already reduced on the device is all the origin needs."""
+    c, gs = g17[f"{name}_coord"], g17[f"{name}_grid_size"]
+    g = np.floor(c / gs).astype(np.int64)
+    assert (c / gs).dtype == np.float32
+    assert np.array_equal(g.min(0), np.floor(c.min(0) / gs).astype(np.int64))
+    assert np.array_equal(R.grid_coords(c, None, gs), g - np.floor(c.min(0) / gs).astype(np.int64))
+
+
 # ---- C-ABI ---------------------------------------------------------------------------------------------------------------
 def _declared():
     hdr = open(os.path.join(ROOT, "include", "unipre3d_pointfusion.h")).read()
@@ -121,8 +202,12 @@ def test_scratch_query_and_argument_errors_without_the_device():
     null = None
     assert lib.u3d_pointfusion_minmax(-1, 1, null, null, null, null) == 1
     assert lib.u3d_pointfusion_compact(10, null, null, null, null, null, null, null) == 1
-    assert lib.u3d_pointfusion_voxelize(10, 5, 1, null, null, null, 3, ctypes.c_float(0.02), null, null, null, null) == 1
-    assert lib.u3d_pointfusion_pick(5, 10, 1, null, null, null, null, 3, ctypes.c_float(0.02), 2, 0, null, 0, null, null, null, null,
+    assert lib.u3d_pointfusion_voxelize(10, 5, 1, null, null, null, 3, 0, ctypes.c_float(0.02), null, null, null, null) == 1
+    assert lib.u3d_pointfusion_pick(5, 10, 1, null, null, null, null, 3, 0, ctypes.c_float(0.02), 2, 0, null, 0, null, null, null, null,
+                                    null, null, null) == 1
+    dummy = ctypes.cast(ctypes.create_string_buffer(64), ctypes.c_void_p)   # never read: the origin mode is refused first
+    assert lib.u3d_pointfusion_voxelize(0, 0, 1, null, null, null, 3, 2, ctypes.c_float(0.02), dummy, dummy, dummy, null) == 1
+    assert lib.u3d_pointfusion_pick(0, 0, 1, null, null, null, null, 3, -1, ctypes.c_float(0.02), 0, 0, null, 0, null, null, null, null,
                                     null, null, null) == 1
     assert lib.u3d_pointfusion_gather_forward(0, 8, 16, null, null, null, null) == 0   # empty: nothing to do
 

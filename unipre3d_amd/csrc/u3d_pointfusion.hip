@@ -66,14 +66,22 @@ __device__ __forceinline__ uint32_t set_begin(const int32_t* __restrict__ off, i
 __device__ __forceinline__ int f2o(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
 __device__ __forceinline__ float o2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 
-// numpy's float -> int64 (x86 conversion: NaN and out-of-range give INT64_MIN)
+// numpy's float -> int64 (x86 conversion): exact for every float whose floor fits, |f| < 2^63 (the largest such fp32 is
+// 2^63 - 2^39); NaN and everything else give INT64_MIN (so does -2^63 itself, which fits)
 __device__ __forceinline__ long long floor_i64(float x) {
   const float f = floorf(x);
-  return fabsf(f) < 9.2233715e18f ? (long long)f : LLONG_MIN;
+  return fabsf(f) < 0x1p63f ? (long long)f : LLONG_MIN;
 }
 
-// grid coordinate of one axis exactly as the reference's numpy 1.26 computes it: fp32 subtraction, correctly rounded fp32 division
-__device__ __forceinline__ long long grid_axis(float c, float m, float gs) { return floor_i64(__fdiv_rn(__fsub_rn(c, m), gs)); }
+// grid coordinate of one axis exactly as the reference's numpy 1.26 computes it, with a correctly rounded fp32 division:
+//   origin 0 (min_coord given):  floor((c - m) / gs), the subtraction in fp32
+//   origin 1 (min_coord=None):   floor(c / gs) - floor(m / gs), m the set's own minimum.  The reference subtracts the minimum of
+//                                the floors; floor and the division by gs > 0 are monotone, so that is the floor of the minimum.
+//                                (the difference wraps as numpy's int64 does)
+__device__ __forceinline__ long long grid_axis(int origin, float c, float m, float gs) {
+  if (origin == 0) return floor_i64(__fdiv_rn(__fsub_rn(c, m), gs));
+  return (long long)((unsigned long long)floor_i64(__fdiv_rn(c, gs)) - (unsigned long long)floor_i64(__fdiv_rn(m, gs)));
+}
 
 __device__ __forceinline__ unsigned long long fnv_key(long long g0, long long g1, long long g2) {
   unsigned long long h = 0xcbf29ce484222325ull;
@@ -160,14 +168,14 @@ struct HeadOp {      // segment heads of the sorted (set, key) sequence; rank = 
 
 // ---- keys and the stable LSD radix sort of (set, key, index) -------------------------------------------------------------
 __global__ __launch_bounds__(NT) void key_kernel(int n_fixed, const int32_t* __restrict__ n_dev, int S, const int32_t* __restrict__ off,
-                                                 const float* __restrict__ coord, const float* __restrict__ minc, int ms, float gs,
-                                                 unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
+                                                 const float* __restrict__ coord, const float* __restrict__ minc, int ms, int origin,
+                                                 float gs, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
   const uint32_t n = n_fixed >= 0 ? (uint32_t)n_fixed : (uint32_t)*n_dev;
   const uint32_t i = blockIdx.x * NT + threadIdx.x;
   if (i >= n) return;
   const float* m = minc + (size_t)set_of(off, S, i) * ms;
   const float* c = coord + (size_t)i * 3;
-  keys[i] = fnv_key(grid_axis(c[0], m[0], gs), grid_axis(c[1], m[1], gs), grid_axis(c[2], m[2], gs));
+  keys[i] = fnv_key(grid_axis(origin, c[0], m[0], gs), grid_axis(origin, c[1], m[1], gs), grid_axis(origin, c[2], m[2], gs));
   vals[i] = i;
 }
 
@@ -262,8 +270,8 @@ __global__ __launch_bounds__(NT) void count_max_kernel(int32_t* __restrict__ met
 }
 
 __global__ __launch_bounds__(NT) void pick_kernel(int M, int S, const int32_t* __restrict__ off, const int32_t* __restrict__ voxel_off,
-                                                  const float* __restrict__ coord, const float* __restrict__ minc, int ms, float gs,
-                                                  int mode, int part, const int64_t* __restrict__ draws, unsigned long long seed,
+                                                  const float* __restrict__ coord, const float* __restrict__ minc, int ms, int origin,
+                                                  float gs, int mode, int part, const int64_t* __restrict__ draws, unsigned long long seed,
                                                   const int32_t* __restrict__ src_map, const uint32_t* __restrict__ starts,
                                                   const uint32_t* __restrict__ vals, const int32_t* __restrict__ setmax,
                                                   int64_t* __restrict__ out_index, float* __restrict__ out_coord,
@@ -282,7 +290,7 @@ __global__ __launch_bounds__(NT) void pick_kernel(int M, int S, const int32_t* _
   const float* m = minc + (size_t)s * ms;
   for (int a = 0; a < 3; ++a) {
     out_coord[(size_t)v * 3 + a] = c[a];
-    out_grid[(size_t)v * 3 + a] = grid_axis(c[a], m[a], gs);
+    out_grid[(size_t)v * 3 + a] = grid_axis(origin, c[a], m[a], gs);
   }
   if (out_src) out_src[v] = src_map ? src_map[idx] : (int32_t)idx;
 }
@@ -372,7 +380,9 @@ int u3d_pointfusion_compact(int P, const float* uc4, const float* box, float* co
 }
 
 int u3d_pointfusion_voxelize(int n_max, int n, int n_sets, const int32_t* set_offsets, const float* coord, const float* min_coord,
-                             int min_stride, float grid_size, int32_t* meta, int32_t* voxel_offsets, void* scratch, void* stream) {
+                             int min_stride, int origin, float grid_size, int32_t* meta, int32_t* voxel_offsets, void* scratch,
+                             void* stream) {
+  if (origin != 0 && origin != 1) return 1;
   if (n_max < 0 || n > n_max || n_sets < 1 || !meta || !voxel_offsets || !scratch || (n_sets > 1 && !set_offsets)) return 1;
   if (n_max > 0 && (!coord || !min_coord || min_stride < 3)) return 1;
   if (!(grid_size > 0.f)) return 1;
@@ -382,7 +392,8 @@ int u3d_pointfusion_voxelize(int n_max, int n, int n_sets, const int32_t* set_of
   setup_kernel<<<blocks(n_sets + 1, NT), NT, 0, st>>>(n, meta, n_sets, s.setmax);
   if (n_max > 0) {
     const int nb = blocks(n_max, TILE);
-    key_kernel<<<blocks(n_max, NT), NT, 0, st>>>(-1, meta, n_sets, set_offsets, coord, min_coord, min_stride, grid_size, s.keys[0], s.vals[0]);
+    key_kernel<<<blocks(n_max, NT), NT, 0, st>>>(-1, meta, n_sets, set_offsets, coord, min_coord, min_stride, origin, grid_size, s.keys[0],
+                                                        s.vals[0]);
     const int passes = 8 + set_passes(n_sets);
     for (int p = 0; p < passes; ++p) {
       const int a = p & 1;
@@ -404,17 +415,18 @@ int u3d_pointfusion_voxelize(int n_max, int n, int n_sets, const int32_t* set_of
 }
 
 int u3d_pointfusion_pick(int M, int n_max, int n_sets, const int32_t* set_offsets, const int32_t* voxel_offsets, const float* coord,
-                         const float* min_coord, int min_stride, float grid_size, int mode, int part, const int64_t* draws, uint64_t seed,
-                         const int32_t* src_map, int64_t* out_index, float* out_coord, int64_t* out_grid, int32_t* out_src,
+                         const float* min_coord, int min_stride, int origin, float grid_size, int mode, int part, const int64_t* draws,
+                         uint64_t seed, const int32_t* src_map, int64_t* out_index, float* out_coord, int64_t* out_grid, int32_t* out_src,
                          const void* scratch, void* stream) {
+  if (origin != 0 && origin != 1) return 1;
   if (M < 0 || M > n_max || n_sets < 1 || (mode != 0 && mode != 1) || part < 0 || (n_sets > 1 && !set_offsets)) return 1;
   if (M == 0) return 0;
   if (!voxel_offsets || !coord || !min_coord || min_stride < 3 || !out_index || !out_coord || !out_grid || !scratch) return 1;
   Scratch s;
   carve(const_cast<void*>(scratch), n_max, n_sets, &s);
   const int fb = final_buffer(n_sets);
-  pick_kernel<<<blocks(M, NT), NT, 0, (hipStream_t)stream>>>(M, n_sets, set_offsets, voxel_offsets, coord, min_coord, min_stride, grid_size,
-                                                             mode, part, draws, (unsigned long long)seed, src_map, s.starts, s.vals[fb],
+  pick_kernel<<<blocks(M, NT), NT, 0, (hipStream_t)stream>>>(M, n_sets, set_offsets, voxel_offsets, coord, min_coord, min_stride, origin,
+                                                             grid_size, mode, part, draws, (unsigned long long)seed, src_map, s.starts, s.vals[fb],
                                                              s.setmax, out_index, out_coord, out_grid, out_src);
   return launched();
 }

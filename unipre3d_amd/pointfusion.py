@@ -4,7 +4,9 @@ libunipre3d_pointfusion.so (include/unipre3d_pointfusion.h).  The reference copi
 hash / argsort / unique; here the points stay on the device and each call reads one 4-word record to size its outputs.
 
 Semantics pinned (tests/pointfusion_ref.py restates them in numpy):
-  grid = floor(fp32(fp32(coord - min_coord) / grid_size)), key = the reference's FNV loop (multiply, then xor) over the three axes,
+  grid = floor(fp32(fp32(coord - min_coord) / grid_size)) with an explicit min_coord (what PointFusion passes), and with min_coord=None
+  the reference's default origin g = floor(fp32(coord / grid_size)), grid = g - g.min(0) (the cells of the absolute grid, not cells
+  anchored at coord.min(0)); float -> int64 as numpy on x86 (exact where the floor fits, INT64_MIN otherwise); key = the reference's FNV loop (multiply, then xor) over the three axes,
   voxels in ascending key order, points inside a voxel in ascending index order, train pick = start + r % count with
   r in [0, count.max()) (replayed from `draws`, or drawn on the device from a seed taken from torch's CPU generator), test pick
   part i = start + i % count.
@@ -22,7 +24,7 @@ from . import _lib
 from ._lib import check, on_device, stream_ptr
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_pointfusion.so")
-ABI_VERSION = 1
+ABI_VERSION = 2
 MODES = {"train": 0, "test": 1}
 
 _i, _f, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
@@ -31,8 +33,8 @@ SIGNATURES = {   # include/unipre3d_pointfusion.h
     "u3d_pointfusion_scratch_bytes": (ctypes.c_size_t, [_i, _i]),
     "u3d_pointfusion_minmax": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
     "u3d_pointfusion_compact": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "u3d_pointfusion_voxelize": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
-    "u3d_pointfusion_pick": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_pointfusion_voxelize": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "u3d_pointfusion_pick": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _i, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "u3d_pointfusion_inverse": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "u3d_pointfusion_gather_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "u3d_pointfusion_gather_backward": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -58,16 +60,16 @@ def _min_rows(min_coord, S, dev):
     return m
 
 
-def _voxelize(coord, grid_size, mins, min_stride, S, offsets, n_max, n, scratch, meta):
+def _voxelize(coord, grid_size, mins, min_stride, origin, S, offsets, n_max, n, scratch, meta):
     dev = coord.device
     voxel_offsets = torch.empty(S + 1, dtype=torch.int32, device=dev)
     check(load().u3d_pointfusion_voxelize(n_max, n, S, _lib.ptr(offsets), _lib.ptr(coord), _lib.ptr(mins), min_stride,
-                                          float(np.float32(grid_size)), _lib.ptr(meta), _lib.ptr(voxel_offsets), _lib.ptr(scratch),
+                                          origin, float(np.float32(grid_size)), _lib.ptr(meta), _lib.ptr(voxel_offsets), _lib.ptr(scratch),
                                           stream_ptr(dev)), "u3d_pointfusion_voxelize", named=False)
     return voxel_offsets
 
 
-def _pick(M, n_max, S, offsets, voxel_offsets, coord, mins, min_stride, grid_size, mode, part, draws, generator, src_map, scratch):
+def _pick(M, n_max, S, offsets, voxel_offsets, coord, mins, min_stride, origin, grid_size, mode, part, draws, generator, src_map, scratch):
     dev = coord.device
     if mode not in MODES:
         raise ValueError(f"mode must be 'train' or 'test', got {mode!r}")
@@ -81,7 +83,7 @@ def _pick(M, n_max, S, offsets, voxel_offsets, coord, mins, min_stride, grid_siz
     grid = torch.empty(M, 3, dtype=torch.int64, device=dev)
     src = torch.empty(M, dtype=torch.int32, device=dev) if src_map is not None else None
     check(load().u3d_pointfusion_pick(M, n_max, S, _lib.ptr(offsets), _lib.ptr(voxel_offsets), _lib.ptr(coord), _lib.ptr(mins),
-                                      min_stride, float(np.float32(grid_size)), MODES[mode], int(part), _lib.ptr(draws), seed,
+                                      min_stride, origin, float(np.float32(grid_size)), MODES[mode], int(part), _lib.ptr(draws), seed,
                                       _lib.ptr(src_map), _lib.ptr(index), _lib.ptr(out_coord), _lib.ptr(grid), _lib.ptr(src),
                                       _lib.ptr(scratch), stream_ptr(dev)), "u3d_pointfusion_pick", named=False)
     return index, out_coord, grid, src
@@ -91,7 +93,9 @@ def grid_sample(coord, grid_size=0.02, min_coord=None, mode="train", draws=None,
                 generator=None):
     """pointcept's GridSample(hash_type="fnv", return_grid_coord=True) on the device.
 
-    coord (N,3) fp32 on the device; min_coord: (3,) or one row per set, None = each set's own minimum (computed on the device).
+    coord (N,3) fp32 on the device; min_coord: (3,) or one row per set: grid = floor((coord - min_coord) / grid_size).  None = the
+    reference's default origin, per set: g = floor(coord / grid_size), grid = g - g.min(0) (computed on the device from the set's own
+    minimum; NaN coordinates are not pinned on this path).
     mode="train" picks one point per voxel (draws: one recorded int per voxel, else a seeded device draw); mode="test" returns
     part `part` (start + part % count).  sizes: a ragged batch of sets stored back to back; the voxels come out grouped by set and each
     group equals a single-set call.  Returns a dict: index (M,) int64 (set-local point index of each voxel's pick), coord (M,3),
@@ -119,15 +123,15 @@ def grid_sample(coord, grid_size=0.02, min_coord=None, mode="train", draws=None,
         mins = torch.empty(S, 6, dtype=torch.float32, device=dev)
         check(lib.u3d_pointfusion_minmax(N, S, _lib.ptr(offsets), _lib.ptr(coord), _lib.ptr(mins), stream_ptr(dev)),
               "u3d_pointfusion_minmax", named=False)
-        stride = 6
+        stride, origin = 6, 1
     else:
-        mins, stride = _min_rows(min_coord, S, dev), 3
+        mins, stride, origin = _min_rows(min_coord, S, dev), 3, 0
     scratch = torch.empty(lib.u3d_pointfusion_scratch_bytes(N, S), dtype=torch.uint8, device=dev)
     meta = torch.empty(4, dtype=torch.int32, device=dev)
-    voxel_offsets = _voxelize(coord, grid_size, mins, stride, S, offsets, N, N, scratch, meta)
+    voxel_offsets = _voxelize(coord, grid_size, mins, stride, origin, S, offsets, N, N, scratch, meta)
     _, M, max_count, _ = meta.tolist()              # the call's one device -> host read
-    index, out_coord, grid, _ = _pick(M, N, S, offsets, voxel_offsets, coord, mins, stride, grid_size, mode, part, draws, generator,
-                                      None, scratch)
+    index, out_coord, grid, _ = _pick(M, N, S, offsets, voxel_offsets, coord, mins, stride, origin, grid_size, mode, part, draws,
+                                      generator, None, scratch)
     out = {"index": index, "coord": out_coord, "grid_coord": grid, "voxel_sizes": (voxel_offsets[1:] - voxel_offsets[:-1]).long(),
            "max_count": max_count}
     if return_inverse:
@@ -168,7 +172,9 @@ class _PixelGather(torch.autograd.Function):
 
 
 def pixel_gather(feat_2d_all, src_pixel):
-    """(M,C) rows of the NCHW features at flat (view, row, column) pixel indices src_pixel (int32); differentiable in feat_2d_all."""
+    """(M,C) rows of the NCHW features at flat (view, row, column) pixel indices src_pixel (int32); differentiable in feat_2d_all.
+    src_pixel must name every pixel at most once (as a grid sample's picks do): the backward writes each picked pixel's row, it does
+    not sum repeats."""
     on_device("pointfusion", feat_2d_all, src_pixel)
     return _PixelGather.apply(feat_2d_all, src_pixel.to(torch.int32).contiguous())
 
@@ -197,11 +203,11 @@ def fuse_pixels(feat_2d_all, unprojected_coord, init_coord, grid_size=0.02, mode
     src_of_point = torch.empty(P, dtype=torch.int32, device=dev)
     check(lib.u3d_pointfusion_compact(P, _lib.ptr(uc), _lib.ptr(box), _lib.ptr(coord), _lib.ptr(src_of_point), _lib.ptr(meta),
                                       _lib.ptr(scratch), stream_ptr(dev)), "u3d_pointfusion_compact", named=False)
-    voxel_offsets = _voxelize(coord, grid_size, box, 6, 1, None, P, -1, scratch, meta)
+    voxel_offsets = _voxelize(coord, grid_size, box, 6, 0, 1, None, P, -1, scratch, meta)
     n, M, _, _ = meta.tolist()                      # the call's one device -> host read
     if n == 0:
         return None
-    _, out_coord, grid, src = _pick(M, P, 1, None, voxel_offsets, coord, box, 6, grid_size, mode, part, draws, generator,
+    _, out_coord, grid, src = _pick(M, P, 1, None, voxel_offsets, coord, box, 6, 0, grid_size, mode, part, draws, generator,
                                     src_of_point, scratch)
     return {"coord": out_coord, "grid_coord": grid, "feat": _PixelGather.apply(feat_2d_all, src), "src_pixel": src, "n": n}
 
