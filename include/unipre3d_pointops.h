@@ -26,6 +26,8 @@
  *   u3d_three_interpolate_grad   <- three_interpolate_grad_wrapper(b, c, n, m, grad_out (B,C,N), idx, weight, grad_points (B,C,M))
  *        (:23, interpolate_gpu.cu:127-148) ACCUMULATES grad_out * weight into grad_points with float atomics; zero it first
  *        (openpoints/models/layers/upsampling.py:86).
+ *   u3d_group_points_grad_rows, u3d_three_interpolate_grad_rows, u3d_group_points_form, u3d_three_interpolate_form
+ *        Host-arithmetic queries (below): which kernel a shape launches, for tests that must reach every one of them.
  *
  * Furthest point sampling over a grid of workgroups (csrc/u3d_fps_grid.h; DESIGN.md, "Furthest point sampling over a grid of workgroups"):
  * one cloud is cut into slices of P = u3d_fps_grid_points_per_workgroup() rows, one workgroup per slice, which meet once per selection.
@@ -103,6 +105,17 @@ int u3d_three_interpolate_grad(int b, int c, int n, int m, const float* grad_out
  */
 int u3d_group_points_grad_rows(int b, int c, int n);
 int u3d_three_interpolate_grad_rows(int b, int c, int m);
+
+/*
+ * Which FORWARD kernel a call launches, likewise through the helper the launch itself uses; host arithmetic on the shape and on the
+ * pointers' values, no device is touched and nothing is dereferenced.
+ *   u3d_group_points_form       1: the vector kernel (four outputs per thread: npoints * nsample a multiple of 4, idx and out on 16-byte
+ *                               boundaries, at most 65535 chunks of 1024 outputs), 0: the scalar kernel.  u3d_gather_points is
+ *                               u3d_group_points with nsample = 1 and selects alike.
+ *   u3d_three_interpolate_form  1: the kernel that stages channel rows of the known cloud in LDS (0 < m <= 2048), 0: the global-gather kernel.
+ */
+int u3d_group_points_form(int npoints, int nsample, const void* idx, const void* out);
+int u3d_three_interpolate_form(int c, int m);
 
 #ifdef __cplusplus
 }

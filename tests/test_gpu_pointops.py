@@ -139,6 +139,7 @@ def test_gradient_kernels_beyond_the_lds_rows():
         w = rng.rand(2, n, 3).astype(np.float32)
         f = torch.from_numpy(feats).cuda().requires_grad_(True)
         out = pointops.three_interpolate(f, torch.from_numpy(idx).cuda(), torch.from_numpy(w).cuda())
+        assert np.array_equal(out.detach().cpu().numpy(), po.three_interpolate(feats, idx, w))   # (m = 17000: the global-gather forward)
         go = rng.randn(*out.shape).astype(np.float32)
         out.backward(torch.from_numpy(go).cuda())
         gref = po.three_interpolate_grad(go, idx, w, m)

@@ -715,6 +715,15 @@ inline int grad_rows(int len, int b, int c) {
 }
 inline int group_grad_rows(int b, int c, int n) { return grad_rows(n, b, c); }
 inline int interp_grad_rows(int b, int c, int m) { return m > 0 ? grad_rows(m, b, c) : 0; }
+// which forward kernel u3d_group_points / u3d_three_interpolate launch; the u3d_*_form queries answer through the same helpers (host
+// arithmetic on the shape and on the pointers' VALUES: nothing is dereferenced).  Group: the vector kernel needs whole int4 / float4
+// accesses (total % 4 == 0, idx and out on 16 bytes) and its output chunks in grid y; interpolate: IL_CB rows of m floats within 32 KB of LDS.
+inline bool group_vec_form(long long total, const void* idx, const void* out) {
+  return total > 0 && total % 4 == 0 && aligned16(idx) && aligned16(out) && (total / 4 + 255) / 256 <= 65535;
+}
+inline bool interp_lds_form(int c, int m) {
+  return m > 0 && (size_t)m * IL_CB * sizeof(float) <= 32768 && (c + IL_CB - 1) / IL_CB <= 65535;
+}
 
 // launch KERNEL<..., CM> for the process-wide contraction mode
 #define U3D_PO_LAUNCH_CM(KERNEL, ...)                                                                 \
@@ -875,7 +884,7 @@ int u3d_group_points(int b, int c, int n, int npoints, int nsample, const float*
   if (b > 65535 || c > 65535) return 1;
   if (!points || !idx || !out) return 1;
   const int total = npoints * nsample;
-  if (total % 4 == 0 && aligned16(idx) && aligned16(out) && (total / 4 + 255) / 256 <= 65535)
+  if (group_vec_form(total, idx, out))
     hipLaunchKernelGGL(group_points_vec_kernel, dim3((c + GP_CH - 1) / GP_CH, (total / 4 + 255) / 256, b), dim3(256), 0, (hipStream_t)stream,
                        c, n, total, points, idx, out);
   else
@@ -930,7 +939,7 @@ int u3d_three_interpolate(int b, int c, int m, int n, const float* points, const
   if (b == 0 || c == 0 || n == 0) return 0;
   if (b > 65535 || (c + IC_CH - 1) / IC_CH > 65535) return 1;
   if (!points || !idx || !weight || !out) return 1;
-  if (m > 0 && (size_t)m * IL_CB * sizeof(float) <= 32768 && (c + IL_CB - 1) / IL_CB <= 65535) {
+  if (interp_lds_form(c, m)) {
     U3D_PO_LAUNCH_CM(three_interpolate_lds_kernel, dim3((n + 256 * IL_PT - 1) / (256 * IL_PT), (c + IL_CB - 1) / IL_CB, b), dim3(256),
                      sizeof(float) * (size_t)m * IL_CB, (hipStream_t)stream, c, m, n, points, idx, weight, out);
   } else {
@@ -963,6 +972,11 @@ int u3d_three_interpolate_grad(int b, int c, int n, int m, const float* grad_out
 
 int u3d_group_points_grad_rows(int b, int c, int n) { return group_grad_rows(b, c, n); }
 int u3d_three_interpolate_grad_rows(int b, int c, int m) { return interp_grad_rows(b, c, m); }
+int u3d_group_points_form(int npoints, int nsample, const void* idx, const void* out) {
+  if (npoints < 0 || nsample < 0) return 0;
+  return group_vec_form((long long)npoints * nsample, idx, out) ? 1 : 0;
+}
+int u3d_three_interpolate_form(int c, int m) { return interp_lds_form(c, m) ? 1 : 0; }
 
 int u3d_pointops_set_contraction(int mode) {
   if (mode != U3D_PO_FMA_LLVM && mode != U3D_PO_FMA_CHAIN && mode != U3D_PO_NO_FMA) return 1;

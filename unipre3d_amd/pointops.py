@@ -47,6 +47,8 @@ SIGNATURES = {   # include/unipre3d_pointops.h
     "u3d_pointops_get_contraction": (_i, []),
     "u3d_group_points_grad_rows": (_i, [_i, _i, _i]),
     "u3d_three_interpolate_grad_rows": (_i, [_i, _i, _i]),
+    "u3d_group_points_form": (_i, [_i, _i, _vp, _vp]),
+    "u3d_three_interpolate_form": (_i, [_i, _i]),
 }
 EXPORTS = tuple(SIGNATURES)
 
