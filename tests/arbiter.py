@@ -117,11 +117,14 @@ class _OracleRender(torch.autograd.Function):
         return (None, f("means3D"), f("opacities"), f("scales"), f("rotations"), f("shs")) + (None,) * 11
 
 
-def _activate(b, raw, center, sh_degree):
-    """Gaussians of ONE item from its raw head output (1,C,P) in raw's dtype, through the reference's activations (head.py, G2)."""
+def _activate(b, raw, center, sh_degree, isotropic=False):
+    """Gaussians of ONE item from its raw head output (1,C,P) in raw's dtype, through the reference's activations (head.py, G2).
+    isotropic: cfg.model.isotropic, which only the object branch has."""
     from unipre3d_amd import head
+    if isotropic and b.level != "object":
+        raise ValueError("the isotropic head variant exists at object level only")
     if b.level == "object":
-        g = head.process_object_output(raw, center, b.offset_scale, sh_degree)
+        g = head.process_object_output(raw, center, b.offset_scale, sh_degree, isotropic=isotropic)
         return {k: x[0] for k, x in g.items()}
     C, P = raw.shape[1], raw.shape[2]
     flat = raw.permute(0, 2, 1).reshape(P, C)
@@ -130,7 +133,7 @@ def _activate(b, raw, center, sh_degree):
 
 
 def head_grad_arbiter(oracle_mod, b, bi, v, H, W, n_views_total, loss_kind, dtype=np.float64, sh_degree=1,
-                      non_bg_rate=4.0, bg_rate=1.0, exact_aa_grad=False, loss_scale=1.0, antialiasing=True, discrete="fp32"):
+                      non_bg_rate=4.0, bg_rate=1.0, exact_aa_grad=False, loss_scale=1.0, antialiasing=True, discrete="fp32", isotropic=False):
     """d loss / d raw[bi] ((C, P), the reference's (B, 23, N) layout) where loss = render loss over ALL n_views_total views'
     pixels but only view (bi, v) differs from its target -- i.e. the per-view contribution the fused kernels can be made to
     isolate by setting gt = rendered for every other view.  Returns (gradient (C,P) ndarray, loss value, image (3,H,W))."""
@@ -138,7 +141,7 @@ def head_grad_arbiter(oracle_mod, b, bi, v, H, W, n_views_total, loss_kind, dtyp
     tdt = torch.float32 if np.dtype(dtype) == np.float32 else torch.float64
     raw = b.raw[bi:bi + 1].detach().cpu().to(tdt).clone().requires_grad_(True)
     center = b.center[bi:bi + 1].detach().cpu().to(tdt)
-    g = _activate(b, raw, center, sh_degree)
+    g = _activate(b, raw, center, sh_degree, isotropic)
     t = math.tan(b.fov_deg * math.pi / 360)
     shs = head.concat_sh(g["features_dc"], g["features_rest"])
     disc32 = None
@@ -146,7 +149,7 @@ def head_grad_arbiter(oracle_mod, b, bi, v, H, W, n_views_total, loss_kind, dtyp
         # the arbiter: fp64 arithmetic under the discrete decisions (cull, radius, rectangle, fp32 depth order with index ties) of the
         # fp32 chain -- fp32 activations of the fp32 head output through the fp32 restatement, i.e. what the reference's operator sees
         with torch.no_grad():
-            g32 = _activate(b, b.raw[bi:bi + 1].detach().cpu().float(), b.center[bi:bi + 1].detach().cpu().float(), sh_degree)
+            g32 = _activate(b, b.raw[bi:bi + 1].detach().cpu().float(), b.center[bi:bi + 1].detach().cpu().float(), sh_degree, isotropic)
             disc32 = (g32["xyz"], g32["opacity"], g32["scaling"], g32["rotation"], head.concat_sh(g32["features_dc"], g32["features_rest"]))
     c = lambda x: x.detach().cpu()
     img = _OracleRender.apply(oracle_mod, g["xyz"], g["opacity"], g["scaling"], g["rotation"], shs, c(b.world_view[bi, v]),

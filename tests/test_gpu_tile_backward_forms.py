@@ -19,22 +19,12 @@ import torch
 
 from arbiter import TOL, head_grad_arbiter, oracle_view
 from conftest import rel_l2
+from gradient_rows import fused_step, place
 from scenes import cotangents
 
 pytestmark = pytest.mark.gpu
 
 GAP_MAX = 0.3 * TOL
-
-
-def place(b, i, px, py, z):
-    """Put Gaussian i of item 0 where view (0, 0) projects it to pixel coordinates (px, py) (integers are pixel centres) at view depth z:
-    the head's offset channels are zeroed (tanh(0) = 0), so the position is the centre."""
-    H, W = b.gt.shape[-2:]
-    t = math.tan(b.fov_deg * math.pi / 360)
-    pv = torch.tensor([((2 * px + 1) / W - 1) * t * z, ((2 * py + 1) / H - 1) * t * z, z, 1.0], dtype=torch.float64)
-    pw = pv @ torch.linalg.inv(b.world_view[0, 0].double())
-    b.raw[0, 0:3, i] = 0.0
-    b.center[0, i] = pw[:3].float()
 
 
 def needle_scene(H, W, cx, cy, seed=11):
@@ -79,17 +69,6 @@ def long_scene(seed=7, H=32, W=32):
     b = synthetic.make_batch(1, 130, 1, H, W, level="object", seed=seed)
     b.raw[0, 3] = -3.0
     return b
-
-
-def fused_step(bd, single_pass=True):
-    from unipre3d_amd import fused
-    H, W = bd.gt.shape[-2:]
-    h = bd.raw.permute(0, 2, 1).contiguous().requires_grad_(True)
-    loss, img, _ = fused.render_loss_fused(h, bd.center, bd.world_view, bd.full_proj, bd.camera_center, bd.gt, bd.bg, bd.fov_deg, H, W,
-                                           level=bd.level, offset_scale=bd.offset_scale, loss_kind="l2", single_pass=single_pass)
-    loss.backward()
-    torch.cuda.synchronize()
-    return loss.detach(), img.detach(), h.grad.detach()
 
 
 def check_fused(oracle_mod, b, what):
