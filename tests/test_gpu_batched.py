@@ -203,6 +203,41 @@ def test_backward_is_run_to_run_deterministic():
                 assert rel_l2(g.cpu().numpy(), grads[0][1].cpu().numpy()) < tol
 
 
+@pytest.mark.parametrize("level,kind,P,B,H,W", [("object", "focal_l2", 24, 33, 80, 112), ("scene", "l2", 300, 22, 80, 128)])
+def test_reduce_group_loops_equal_one_call_per_item(level, kind, P, B, H, W):
+    """bwd_reduce_kernel sums a slice's tiles in groups (32 in flight in the single-block form, 16 in the other) and then one by one.
+    bwd_reduce_split (u3d_render.hip) gives s = max((T + 64) / 128, 256 / NV), capped at T / 8 and 32, and a slice ceil(T / s) tiles:
+    every other small case of the suite (NV <= 16, T <= 64) gets at most 15 tiles per slice -- the one-by-one loop alone.  Here, V = 4:
+      object  P = 24,  NV = 132, T = 7 x 5 = 35: s = max(0, 1) = 1 -> one slice of 35 = a group of 32 + 3 singles   (P <= 256: form <1>)
+      scene   P = 300, NV = 88,  T = 8 x 5 = 40: s = max(0, 2) = 2 -> two slices of 20 = a group of 16 + 4 singles  (form <2>; faint
+              opacities, so that rows beyond the first 64 sorted positions occur)
+    against one call per item (NV = 4: s = min(64, T / 8) -> slices of 9 resp. 8 tiles, the singles-only class the oracle-backed tests
+    pin), fused step and two-pass route.  Bars as in test_gpu_ragged.py::test_ragged_fused_step_equals_one_call_per_set (the batched
+    loss scales every seed by 1 / B in-kernel, so every term of the gradient sum is re-rounded)."""
+    from unipre3d_amd import fused
+    V = 4
+    _, bd = _batch(B, P, V, H, W, level=level, seed=71)
+    if level == "scene":
+        bd.raw[:, 3] -= 3.0
+    head = bd.raw.permute(0, 2, 1).contiguous()
+
+    def step(h, sel, single_pass):
+        loss, img, _ = fused.render_loss_fused(h, bd.center[sel], bd.world_view[sel], bd.full_proj[sel], bd.camera_center[sel], bd.gt[sel], bd.bg,
+                                               bd.fov_deg, H, W, level=level, offset_scale=bd.offset_scale, loss_kind=kind, single_pass=single_pass)
+        loss.backward()
+        return loss.item(), img.detach(), h.grad
+
+    for single_pass in (True, False):
+        loss, img, grad = step(head.clone().requires_grad_(True), slice(None), single_pass)
+        ref = [step(head[i:i + 1].clone().requires_grad_(True), slice(i, i + 1), single_pass) for i in range(B)]
+        torch.cuda.synchronize()
+        assert abs(loss - sum(r[0] for r in ref) / B) <= 1e-6 * abs(loss), single_pass
+        for i, (_, ref_img, ref_grad) in enumerate(ref):
+            assert torch.equal(img[i * V:(i + 1) * V], ref_img), (single_pass, i)
+            e = rel_l2((grad[i] * B).cpu().numpy(), ref_grad[0].cpu().numpy())
+            assert e < 2e-5, (single_pass, i, e)
+
+
 def test_fused_sh_degree0_and_uneven_shapes():
     """C = 14 channels (max_sh_degree 0), P not a multiple of 64/256, image not a multiple of 16, 1 view per object."""
     from unipre3d_amd import fused, head, losses, renderer, synthetic

@@ -832,9 +832,43 @@ __global__ __launch_bounds__(TILE_WAVES * U3D_WAVE) U3D_FULL_OCCUPANCY void rend
 // One thread per (position, component) element of a tile's [64][10] block, so a tile is one contiguous read; only the
 // positions some tile of the slice touched (cmax, usually ~20 of 64) are read at all.
 constexpr int REDUCE_THREADS = U3D_WAVE * 10;
-// tiles in flight per thread: 32 in the single-block kernel (object level), 16 in the generic one (measured:
-// C3 10.1 -> 9.3 us, C4 17.0 -> 15.5, C5 13.0 -> 11.8 with 16; C2 11.3 -> 11.6; 64 is slower everywhere)
-constexpr int RU = 16, RU1 = 32;
+// The two forms of the kernel, by PB = u3d_part_blocks(d):
+//   PB == 1 (P <= 256, object level): every tile's rows fit the first 64 positions -- the block loop and the per-tile stride fold away;
+//   PB  > 1 (scene level): the block loop, and STEP -- the zero-fill rows and the touched list of the fused step.  Both belong to the
+//   sparse backward, which exists only for P > U3D_LDS_SORT_MAX, far above P <= 256: the single-block form compiles them out.
+// RU, tiles in flight per thread: 32 in the single-block form, 16 in the other (measured: C3 10.1 -> 9.3 us, C4 17.0 -> 15.5,
+// C5 13.0 -> 11.8 with 16; C2 11.3 -> 11.6; 64 is slower everywhere).
+// One source, measured against the hand copy `<1>` replaced (rocprofv3, three alternating pairs): C2 11.32 - 11.41 us against
+// 11.20 - 11.32, two-pass 11.90 - 12.01 against 11.86 - 12.05; `<2>` C3 9.53 - 9.56 against 9.43 - 9.59, C5 13.18 - 13.42 against 13.17 - 13.47.
+template <int PB>
+struct ReduceForm {
+  static constexpr int RU = PB == 1 ? 32 : 16;
+  static constexpr bool STEP = PB > 1;
+};
+static_assert(U3D_LDS_SORT_MAX > 256, "u3d_part_blocks: PB == 1 means P <= 256, which must lie below the sparse backward's threshold");
+
+// Extra row of the reduce grid: fixed-order sum of the per-tile loss partials (replaces a separate launch).  Not loss_reduce_kernel
+// below: that one sums 1024-wide by tree for the two-pass forward -- another order, other bits.
+__device__ __forceinline__ void loss_row(float* sm, int n_loss, const float* __restrict__ loss_partial, float inv_count,
+                                         float* __restrict__ loss_out) {
+  constexpr int NT = REDUCE_THREADS;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  int i = threadIdx.x;
+  for (; i + 3 * NT < n_loss; i += 4 * NT) {
+    a0 += loss_partial[i]; a1 += loss_partial[i + NT]; a2 += loss_partial[i + 2 * NT]; a3 += loss_partial[i + 3 * NT];
+  }
+  for (; i < n_loss; i += NT) a0 += loss_partial[i];
+  sm[threadIdx.x] = (a0 + a1) + (a2 + a3);
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    float v = 0.f;
+    for (int j = threadIdx.x; j < NT; j += 64) v += sm[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (threadIdx.x == 0) loss_out[0] = v * inv_count;
+  }
+}
+
 template <int PB>
 __global__ __launch_bounds__(REDUCE_THREADS) void bwd_reduce_kernel(U3DSpan span, int T, int NK, int nsplit, size_t NG, float half_w, float half_h,
                                                                    const uint32_t* __restrict__ sorted_id,
@@ -847,9 +881,11 @@ __global__ __launch_bounds__(REDUCE_THREADS) void bwd_reduce_kernel(U3DSpan span
                                                                    float* __restrict__ loss_out, uint2* __restrict__ tlist,
                                                                    uint32_t* __restrict__ tcount, float* __restrict__ zero_fill,
                                                                    size_t zero_floats) {
+  constexpr int RU = ReduceForm<PB>::RU;
+  constexpr bool STEP = ReduceForm<PB>::STEP;
   __shared__ double s_sum[U3D_WAVE][10];
   __shared__ uint32_t s_cmax;
-  if ((int)blockIdx.y > nsplit) {
+  if (STEP && (int)blockIdx.y > nsplit) {
     // rows beyond the loss row (U3D_FLAG_SPARSE_BWD): zero-fill the gradient buffer the backward half will scatter into -- 16-byte
     // stores from workgroups that run beside the latency-bound tile chains of the reduction, i.e. off the step's critical path
     const size_t nb = (size_t)gridDim.x * (gridDim.y - nsplit - 1), bid = (size_t)(blockIdx.y - nsplit - 1) * gridDim.x + blockIdx.x;
@@ -860,25 +896,7 @@ __global__ __launch_bounds__(REDUCE_THREADS) void bwd_reduce_kernel(U3DSpan span
     return;
   }
   if ((int)blockIdx.y == nsplit) {
-    // extra row of the grid: fixed-order sum of the per-tile loss partials (replaces a separate launch)
-    if (blockIdx.x != 0) return;
-    float* sm = reinterpret_cast<float*>(&s_sum[0][0]);
-    constexpr int NT = REDUCE_THREADS;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int i = threadIdx.x;
-    for (; i + 3 * NT < n_loss; i += 4 * NT) {
-      a0 += loss_partial[i]; a1 += loss_partial[i + NT]; a2 += loss_partial[i + 2 * NT]; a3 += loss_partial[i + 3 * NT];
-    }
-    for (; i < n_loss; i += NT) a0 += loss_partial[i];
-    sm[threadIdx.x] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      float v = 0.f;
-      for (int j = threadIdx.x; j < NT; j += 64) v += sm[j];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      if (threadIdx.x == 0) loss_out[0] = v * inv_count;
-    }
+    if (blockIdx.x == 0) loss_row(reinterpret_cast<float*>(&s_sum[0][0]), n_loss, loss_partial, inv_count, loss_out);
     return;
   }
   const int view = blockIdx.x, sp = threadIdx.x / 10, k = threadIdx.x - sp * 10;
@@ -896,9 +914,12 @@ __global__ __launch_bounds__(REDUCE_THREADS) void bwd_reduce_kernel(U3DSpan span
   const uint32_t cmax = s_cmax;
   if (cmax == 0u) return;
   constexpr size_t tstride = (size_t)PB * (U3D_WAVE * 10);   // floats per tile
+  // Blocks of 64 sorted positions, while cmax reaches them.  A do-while on purpose: its condition starts with a compile-time `PB > 1`,
+  // so the single-block form is compiled without any loop.  Written as `for (h < PB)`, the one-trip loop goes away only late in the
+  // optimiser, which then makes one load of each group conditional and serial: 13.4 instead of 11.4 us at C2.
+  int h = 0;
 #pragma unroll
-  for (int h = 0; h < PB; ++h) {   // block of 64 sorted positions (PB == 1: exactly the single-block kernel)
-    if (h > 0 && cmax <= (uint32_t)(h * U3D_WAVE)) break;
+  do {
     const uint32_t spos = (uint32_t)(h * U3D_WAVE + sp);
     double a = 0.0;
     if (k < NK && spos < cmax) {
@@ -950,112 +971,15 @@ __global__ __launch_bounds__(REDUCE_THREADS) void bwd_reduce_kernel(U3DSpan span
         if (outv != 0.0) unsafeAtomicAdd(&acc[(size_t)k * NG + g], outv);
         if (k == 0) {
           touched[g] |= U3D_TOUCHED_BIT;   // this (view, Gaussian) has a non-zero row
-          if (touched_words)
-            u3d_mark_touched_list(touched_words, u3d_view_gbase(span, view) + (g - vb), tlist, tcount, (uint32_t)(view / span.vpi), (uint32_t)(g - vb));
+          if (touched_words) {
+            const size_t gi = u3d_view_gbase(span, view) + (g - vb);
+            if constexpr (STEP) u3d_mark_touched_list(touched_words, gi, tlist, tcount, (uint32_t)(view / span.vpi), (uint32_t)(g - vb));
+            else u3d_mark_touched(touched_words, gi);
+          }
         }
       }
     }
-  }
-}
-
-// Single-block form (object level: every tile's rows fit the first 64 positions): the same reduction with the block loop
-// and the per-tile stride folded away (the generic instantiation measured 2 us slower at C2).
-__global__ __launch_bounds__(REDUCE_THREADS) void bwd_reduce1_kernel(U3DSpan span, int T, int NK, int nsplit, size_t NG, float half_w, float half_h,
-                                                                   const uint32_t* __restrict__ sorted_id,
-                                                                   const float4* __restrict__ conic_op,
-                                                                   const float* __restrict__ part,
-                                                                   const uint32_t* __restrict__ part_cnt,
-                                                                   double* __restrict__ acc, uint32_t* __restrict__ touched,
-                                                                   uint32_t* __restrict__ touched_words, int n_loss,
-                                                                   const float* __restrict__ loss_partial, float inv_count,
-                                                                   float* __restrict__ loss_out) {
-  __shared__ double s_sum[U3D_WAVE][10];
-  __shared__ uint32_t s_cmax;
-  if ((int)blockIdx.y == nsplit) {
-    // extra row of the grid: fixed-order sum of the per-tile loss partials (replaces a separate launch)
-    if (blockIdx.x != 0) return;
-    float* sm = reinterpret_cast<float*>(&s_sum[0][0]);
-    constexpr int NT = REDUCE_THREADS;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int i = threadIdx.x;
-    for (; i + 3 * NT < n_loss; i += 4 * NT) {
-      a0 += loss_partial[i]; a1 += loss_partial[i + NT]; a2 += loss_partial[i + 2 * NT]; a3 += loss_partial[i + 3 * NT];
-    }
-    for (; i < n_loss; i += NT) a0 += loss_partial[i];
-    sm[threadIdx.x] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      float v = 0.f;
-      for (int j = threadIdx.x; j < NT; j += 64) v += sm[j];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      if (threadIdx.x == 0) loss_out[0] = v * inv_count;
-    }
-    return;
-  }
-  const int view = blockIdx.x, sp = threadIdx.x / 10, k = threadIdx.x - sp * 10;
-  const int per = (T + nsplit - 1) / nsplit;
-  const int t0 = blockIdx.y * per, t1 = min(T, t0 + per);
-  const uint32_t* cnt = part_cnt + (size_t)view * T;
-  if (threadIdx.x == 0) s_cmax = 0u;
-  __syncthreads();
-  {
-    uint32_t c = 0u;
-    for (int t = t0 + (int)threadIdx.x; t < t1; t += REDUCE_THREADS) c = max(c, cnt[t]);
-    if (c != 0u) atomicMax(&s_cmax, c);
-  }
-  __syncthreads();
-  const uint32_t cmax = s_cmax;
-  if (cmax == 0u) return;
-  double a = 0.0;
-  if (k < NK && (uint32_t)sp < cmax) {
-    const float* base = part + (size_t)view * T * (U3D_WAVE * 10) + threadIdx.x;
-    // loads are unconditional below cmax (rows a tile did not write hold stale bytes, discarded by the select) so that a
-    // whole group of tiles is in flight at once; accumulation order stays ascending in t within each of the two chains
-    double a0 = 0.0, a1 = 0.0;
-    int t = t0;
-    for (; t + RU1 - 1 < t1; t += RU1) {
-      float v[RU1];
-      uint32_t c[RU1];
-#pragma unroll
-      for (int u = 0; u < RU1; ++u) {
-        c[u] = cnt[t + u];
-        v[u] = base[(size_t)(t + u) * (U3D_WAVE * 10)];
-      }
-#pragma unroll
-      for (int u = 0; u < RU1; u += 2) {
-        a0 += (uint32_t)sp < c[u] ? (double)v[u] : 0.0;
-        a1 += (uint32_t)sp < c[u + 1] ? (double)v[u + 1] : 0.0;
-      }
-    }
-    for (; t < t1; ++t) {
-      const float v0 = base[(size_t)t * (U3D_WAVE * 10)];
-      a0 += (uint32_t)sp < cnt[t] ? (double)v0 : 0.0;
-    }
-    a = a0 + a1;
-  }
-  // raw moment sums of this slice -> accumulator values (linear, so slices can be converted independently)
-  s_sum[sp][k] = a;
-  __syncthreads();
-  if (k >= NK || (uint32_t)sp >= cmax) return;
-  double m[U3D_NACC];
-#pragma unroll
-  for (int j = 0; j < U3D_NACC; ++j) m[j] = j < NK ? s_sum[sp][j] : 0.0;
-  bool any = false;
-#pragma unroll
-  for (int j = 0; j < U3D_NACC; ++j) any = any || m[j] != 0.0;
-  if (!any) return;
-  int Pv;
-  size_t vb;
-  u3d_view_span(span, view, Pv, vb);
-  const size_t g = vb + sorted_id[vb + sp];
-  const float4 co = conic_op[g];
-  const double outv = moment_to_acc<double>(k, m, co.x, co.y, co.z, co.w, half_w, half_h);
-  if (outv != 0.0) unsafeAtomicAdd(&acc[(size_t)k * NG + g], outv);
-  if (k == 0) {
-    touched[g] |= U3D_TOUCHED_BIT;   // this (view, Gaussian) has a non-zero row
-    if (touched_words) u3d_mark_touched(touched_words, u3d_view_gbase(span, view) + (g - vb));
-  }
+  } while (PB > 1 && ++h < PB && cmax > (uint32_t)(h * U3D_WAVE));
 }
 
 
@@ -1117,17 +1041,6 @@ struct TileFrame {
   }
 };
 
-// The gradient reduction behind a tile launch: `rows` grid rows per view (the nsplit slices, then the loss row and the zero-fill rows
-// of the fused step); `tail` = what bwd_reduce_kernel takes beyond bwd_reduce1_kernel's list.
-template <typename Kernel, typename... Tail>
-static void launch_reduce(Kernel kern, const u3d_raster_desc& d, const U3DBuffers& b, const TileFrame& tf, int NK, int nsplit, int rows,
-                          double* acc, const float* part, int n_loss, const U3DLoss& loss, float* loss_out, hipStream_t s, Tail... tail) {
-  hipLaunchKernelGGL(kern, dim3(tf.NV, rows), dim3(REDUCE_THREADS), 0, s, u3d_span(d), tf.T, NK, nsplit, tf.NG, 0.5f * (float)d.image_width,
-                     0.5f * (float)d.image_height, b.sorted_id, b.conic_op, part,
-                     reinterpret_cast<const uint32_t*>(part + (size_t)tf.ntiles * BWD_PART_STRIDE), acc, b.clamped, tf.tw, n_loss,
-                     n_loss ? loss.partial : nullptr, n_loss ? loss.inv_count : 0.f, loss_out, tail...);
-}
-
 void u3d_launch_render_fwd(const u3d_raster_desc& d, const U3DBuffers& b, const float* bg, float* out_color,
                            float* out_invdepth, const U3DLoss& loss, hipStream_t s) {
   const TileFrame tf(d, b);
@@ -1141,6 +1054,18 @@ void u3d_launch_render_fwd(const u3d_raster_desc& d, const U3DBuffers& b, const 
 // the instantiation for a call (pb = u3d_part_blocks; the pickers sit below the forward launcher so that the kernels are
 // instantiated, and so emitted, in the order the three launchers name them)
 static inline auto pick_fb(int pb) { return pb == 1 ? render_fb_wave_kernel<1> : render_fb_wave_kernel<U3D_PART_BLOCKS>; }
+static inline auto pick_reduce(int pb) { return pb == 1 ? bwd_reduce_kernel<1> : bwd_reduce_kernel<U3D_PART_BLOCKS>; }
+
+// The gradient reduction behind a tile launch: `rows` grid rows per view (the nsplit slices, then the loss row and the zero-fill rows
+// of the fused step)
+static void launch_reduce(const u3d_raster_desc& d, const U3DBuffers& b, const TileFrame& tf, int pb, int NK, int nsplit, int rows,
+                          double* acc, const float* part, int n_loss, const U3DLoss& loss, float* loss_out, hipStream_t s,
+                          uint2* tlist = nullptr, uint32_t* tcount = nullptr, float* zero_fill = nullptr, size_t zero_floats = 0) {
+  hipLaunchKernelGGL(pick_reduce(pb), dim3(tf.NV, rows), dim3(REDUCE_THREADS), 0, s, u3d_span(d), tf.T, NK, nsplit, tf.NG,
+                     0.5f * (float)d.image_width, 0.5f * (float)d.image_height, b.sorted_id, b.conic_op, part,
+                     reinterpret_cast<const uint32_t*>(part + (size_t)tf.ntiles * BWD_PART_STRIDE), acc, b.clamped, tf.tw, n_loss,
+                     n_loss ? loss.partial : nullptr, n_loss ? loss.inv_count : 0.f, loss_out, tlist, tcount, zero_fill, zero_floats);
+}
 
 void u3d_launch_render_fb(const u3d_raster_desc& d, const U3DBuffers& b, const float* bg, float* out_color,
                           const U3DLoss& loss, double* acc, float* part, float* loss_out, hipStream_t s,
@@ -1181,19 +1106,14 @@ void u3d_launch_render_fb(const u3d_raster_desc& d, const U3DBuffers& b, const f
                      ntiles, tf.tg.magic, tf.NG, b.sorted_id, tf.rect, tf.rect_indirect, b.n_vis, b.xy, b.conic_op, b.rgbd, bg, out_color, acc, part,
                      b.clamped, tf.tw, tl, tc, loss);
   const int nsplit = bwd_reduce_split(tf.T, tf.NV);
-  if (pb == 1) {
-    launch_reduce(bwd_reduce1_kernel, d, b, tf, U3D_NACC - 1, nsplit, nsplit + 1, acc, part, (int)ntiles, loss, loss_out, s);
-  } else {
-    // zero-fill rows (U3D_FLAG_SPARSE_BWD): ~256 extra workgroups of 640 threads, at most one per 64 KB to fill
-    int zrows = 0;
-    if (zero_fill && zero_floats > 0) {
-      const size_t want = (zero_floats * sizeof(float) + 65535) / 65536;
-      zrows = (int)((want < 256 ? want : 256) + (size_t)tf.NV - 1) / tf.NV;
-      if (zrows < 1) zrows = 1;
-    }
-    launch_reduce(bwd_reduce_kernel<U3D_PART_BLOCKS>, d, b, tf, U3D_NACC - 1, nsplit, nsplit + 1 + zrows, acc, part, (int)ntiles, loss,
-                  loss_out, s, tl, tc, zero_fill, zero_floats);
+  // zero-fill rows (U3D_FLAG_SPARSE_BWD, hence never with pb == 1): ~256 extra workgroups of 640 threads, at most one per 64 KB to fill
+  int zrows = 0;
+  if (pb > 1 && zero_fill && zero_floats > 0) {
+    const size_t want = (zero_floats * sizeof(float) + 65535) / 65536;
+    zrows = (int)((want < 256 ? want : 256) + (size_t)tf.NV - 1) / tf.NV;
+    if (zrows < 1) zrows = 1;
   }
+  launch_reduce(d, b, tf, pb, U3D_NACC - 1, nsplit, nsplit + 1 + zrows, acc, part, (int)ntiles, loss, loss_out, s, tl, tc, zero_fill, zero_floats);
 }
 
 static inline auto pick_bwd(bool invd, int pb) {
@@ -1213,9 +1133,5 @@ void u3d_launch_render_bwd(const u3d_raster_desc& d, const U3DBuffers& b, const 
                      tf.T, tf.ntiles, tf.tg.magic, tf.NG, b.sorted_id, tf.rect, tf.rect_indirect, b.xy, b.conic_op, b.rgbd, bg, dL_dcolor, dL_dinvdepth,
                      b.final_T, b.n_contrib, b.tile_last, acc, part, out_color, b.clamped, tf.tw, loss);
   const int nsplit = bwd_reduce_split(tf.T, tf.NV), NK = invd ? U3D_NACC : U3D_NACC - 1;
-  if (pb == 1)
-    launch_reduce(bwd_reduce1_kernel, d, b, tf, NK, nsplit, nsplit, acc, part, 0, loss, nullptr, s);
-  else
-    launch_reduce(bwd_reduce_kernel<U3D_PART_BLOCKS>, d, b, tf, NK, nsplit, nsplit, acc, part, 0, loss, nullptr, s, (uint2*)nullptr,
-                  (uint32_t*)nullptr, (float*)nullptr, (size_t)0);
+  launch_reduce(d, b, tf, pb, NK, nsplit, nsplit, acc, part, 0, loss, nullptr, s);
 }
