@@ -1,0 +1,220 @@
+"""Mamba3D's local norm pooling (openpoints/models/Mamba3D/Mamba3D.py:132-354): `from unipre3d_amd.lnp import LNPBlock` is the switch for
+the first half of every Mamba3DBlock.  GroupFeature's two gathers, K_Norm (one std over the whole gathered tensor, the cat with the
+centre feature, the affine) and K_Pool (the softmax-weighted mean over the K neighbours) are one operator in libunipre3d_lnp.so
+(include/unipre3d_lnp.h, csrc/u3d_lnp.hip): x (B, G, C) in, (B, G, 2C) out, no (B, G, K, .) tensor in between, forward or backward.
+
+  neighbours(center, k)                      the kNN of the centres and its inverse lists, once per model forward (every block shares them)
+  local_norm_pool(x, nb, alpha, beta, eps)   the autograd function
+  LNPBlock                                   the reference's module: same constructor, parameter names and forward(center, feat)
+
+Three departures from the reference's bits: the row maximum is subtracted before exp (the reference's plain exp overflows from v = 88.7
+in fp32), the upper half alpha x + beta is one fma (the reference pools K equal values), and a std of exactly 0 gives zero, not NaN,
+for the variance term of the gradient.
+
+Scope: fp32, 1 <= G <= 1024, 2 <= K <= 32, C a multiple of 4 and at most 512; anything else raises (there is no fallback)."""
+from __future__ import annotations
+
+import ctypes
+import os
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from . import _lib, knn
+from ._lib import check, on_device, stream_ptr
+
+LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_lnp.so")
+ABI_VERSION = 1
+MAX_GROUPS, MAX_K, MAX_CHANNELS = 1024, 32, 512          # include/unipre3d_lnp.h
+
+_i, _f, _vp, _ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong
+SIGNATURES = {   # include/unipre3d_lnp.h
+    "u3d_lnp_abi_version": (_i, []),
+    "u3d_lnp_scratch_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
+    "u3d_lnp_neighbours": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "u3d_lnp_fwd": (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "u3d_lnp_bwd": (_i, [_vp, _ll] + [_vp] * 13 + [_i, _i, _i, _i, _vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+
+
+def load() -> ctypes.CDLL:
+    return _lib.open_library("libunipre3d_lnp.so", SIGNATURES, ("u3d_lnp_abi_version", ABI_VERSION))
+
+
+class Neighbours:
+    """idx (B, G, K) int32 and its inverse lists: ptr (B, G+1) int32, ent (B, G K) int32 with row j's entries e = g K + k, ascending,
+    at ent[b, ptr[b, j]:ptr[b, j+1]].  An index outside [0, G) counts as the row itself everywhere."""
+    __slots__ = ("idx", "ptr", "ent")
+
+    def __init__(self, idx, ptr, ent):
+        self.idx, self.ptr, self.ent = idx, ptr, ent
+
+    @property
+    def k(self):
+        return self.idx.shape[2]
+
+
+def _check_idx(idx):
+    if idx.dim() != 3:
+        raise ValueError(f"idx: expected (B, G, K), got {tuple(idx.shape)}")
+    if idx.dtype not in (torch.int32, torch.int64):
+        raise NotImplementedError(f"idx: dtype {idx.dtype} is not implemented (int32 or int64)")
+    B, G, K = idx.shape
+    if B < 1 or G < 1:
+        raise ValueError(f"idx: an empty tensor {tuple(idx.shape)} is not supported")
+    if G > MAX_GROUPS:
+        raise NotImplementedError(f"idx: G={G} is not implemented (at most {MAX_GROUPS})")
+    if not 2 <= K <= MAX_K:
+        raise NotImplementedError(f"idx: K={K} is not implemented (2 to {MAX_K})")
+
+
+@torch.no_grad()
+def neighbours_from_idx(idx) -> Neighbours:
+    """The inverse lists of a given neighbour table idx (B, G, K) (int64 is narrowed to int32)."""
+    _check_idx(idx)
+    dev = on_device("lnp", idx)
+    idx = idx.to(torch.int32).contiguous()
+    B, G, K = idx.shape
+    ptr = torch.empty(B, G + 1, dtype=torch.int32, device=dev)
+    ent = torch.empty(B, G * K, dtype=torch.int32, device=dev)
+    check(load().u3d_lnp_neighbours(_lib.ptr(idx), _lib.ptr(ptr), _lib.ptr(ent), B, G, K, stream_ptr(dev)), "u3d_lnp_neighbours",
+          named=False)
+    return Neighbours(idx, ptr, ent)
+
+
+@torch.no_grad()
+def neighbours(center, k: int) -> Neighbours:
+    """GroupFeature's search, knn(center, center) with k neighbours, run once, and the inverse lists of its result.  center (B, G, 3)."""
+    if center.dim() != 3 or center.shape[2] != 3:
+        raise ValueError(f"center: expected (B, G, 3), got {tuple(center.shape)}")
+    k = int(k)
+    if center.shape[1] > MAX_GROUPS:
+        raise NotImplementedError(f"center: G={center.shape[1]} is not implemented (at most {MAX_GROUPS})")
+    if not 2 <= k <= MAX_K:
+        raise NotImplementedError(f"k={k} is not implemented (2 to {MAX_K})")
+    on_device("lnp", center)
+    return neighbours_from_idx(knn.knn_query(k, center, center)[1])
+
+
+_search = neighbours      # (LNPBlock.forward has a parameter of that name)
+
+
+def _scratch(nbytes, dev):
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+class _LocalNormPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, alpha, beta, nb, eps):
+        B, G, C = x.shape
+        K = nb.k
+        dev = x.device
+        lib = load()
+        out = torch.empty(B, G, 2 * C, dtype=torch.float32, device=dev)
+        lse = torch.empty(B, G, C, dtype=torch.float32, device=dev)
+        stats = torch.empty(4, dtype=torch.float32, device=dev)
+        scratch = _scratch(lib.u3d_lnp_scratch_bytes(B, G, K, C, 0), dev)
+        check(lib.u3d_lnp_fwd(_lib.ptr(x), x.stride(0), _lib.ptr(nb.idx), _lib.ptr(alpha), _lib.ptr(beta), _lib.ptr(out), _lib.ptr(lse),
+                              _lib.ptr(stats), _lib.ptr(scratch), B, G, K, C, eps, stream_ptr(dev)), "u3d_lnp_fwd", named=False)
+        ctx.save_for_backward(x, alpha, beta, out, lse, stats)
+        ctx.nb = nb
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, alpha, beta, out, lse, stats = ctx.saved_tensors
+        nb = ctx.nb
+        B, G, C = x.shape
+        K = nb.k
+        dev = x.device
+        lib = load()
+        dout = dout.to(torch.float32).contiguous()
+        dx = torch.empty(B, G, C, dtype=torch.float32, device=dev)
+        dalpha, dbeta = torch.empty(2 * C, dtype=torch.float32, device=dev), torch.empty(2 * C, dtype=torch.float32, device=dev)
+        scratch = _scratch(lib.u3d_lnp_scratch_bytes(B, G, K, C, 1), dev)
+        check(lib.u3d_lnp_bwd(_lib.ptr(x), x.stride(0), _lib.ptr(nb.idx), _lib.ptr(nb.ptr), _lib.ptr(nb.ent), _lib.ptr(alpha),
+                              _lib.ptr(beta), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(stats), _lib.ptr(dout), _lib.ptr(dx),
+                              _lib.ptr(dalpha), _lib.ptr(dbeta), _lib.ptr(scratch), B, G, K, C, stream_ptr(dev)), "u3d_lnp_bwd", named=False)
+        return dx, dalpha, dbeta, None, None
+
+
+def local_norm_pool(x, nb: Neighbours, alpha, beta, eps: float = 1e-5):
+    """K_Norm + K_Pool of the reference on x (B, G, C) fp32 -> (B, G, 2C), the layout pre_norm_ft reads.
+
+    With d[b,g,k] = x[b, idx[b,g,k]] - x[b,g], s the std of all of d (one scalar, n - 1 in the denominator) and v = alpha[:C] d / (s + eps)
+    + beta[:C]: out[..., :C] = sum_k softmax_k(v) v and out[..., C:] = alpha[C:] x + beta[C:].  x may be a view with any batch stride whose
+    rows are contiguous (the reference's feat[:, 1:, :]); alpha and beta hold 2C values in any shape (the reference's [1, 1, 1, 2C]).
+    Differentiable with respect to x, alpha and beta.  Kept for the backward: x, out, a (B, G, C) row log-sum-exp and four scalars."""
+    if not isinstance(nb, Neighbours):
+        raise ValueError("nb: expected the result of lnp.neighbours() or lnp.neighbours_from_idx()")
+    if x.dim() != 3:
+        raise ValueError(f"x: expected (B, G, C), got {tuple(x.shape)}")
+    for name, t in (("x", x), ("alpha", alpha), ("beta", beta)):
+        if t.dtype != torch.float32:
+            raise NotImplementedError(f"{name}: dtype {t.dtype} is not implemented (fp32 only)")
+    B, G, C = x.shape
+    if B < 1 or G < 1 or C < 1:
+        raise ValueError(f"x: an empty tensor {tuple(x.shape)} is not supported")
+    if tuple(nb.idx.shape[:2]) != (B, G):
+        raise ValueError(f"nb: built for (B, G) = {tuple(nb.idx.shape[:2])}, x is {tuple(x.shape)}")
+    _check_idx(nb.idx)
+    if (tuple(nb.ptr.shape), tuple(nb.ent.shape)) != ((B, G + 1), (B, G * nb.k)) or \
+            any(t.dtype != torch.int32 or not t.is_contiguous() for t in (nb.idx, nb.ptr, nb.ent)):
+        raise ValueError("nb: idx (B, G, K), ptr (B, G+1) and ent (B, G K) must be contiguous int32 tensors")
+    if alpha.numel() != 2 * C or beta.numel() != 2 * C:
+        raise ValueError(f"alpha, beta: expected 2C = {2 * C} values, got {alpha.numel()} and {beta.numel()}")
+    if G > MAX_GROUPS:
+        raise NotImplementedError(f"x: G={G} is not implemented (at most {MAX_GROUPS})")
+    if C % 4 != 0 or C > MAX_CHANNELS:
+        raise NotImplementedError(f"x: C={C} is not implemented (a multiple of 4, at most {MAX_CHANNELS})")
+    if x.stride(2) != 1 or x.stride(1) != C or x.stride(0) < G * C or x.stride(0) % 4 != 0 or x.data_ptr() % 16 != 0:
+        raise ValueError("x: rows must be contiguous, 16-byte aligned and batch elements must not overlap (call .contiguous())")
+    eps = float(eps)
+    if not 0.0 <= eps < float("inf"):
+        raise ValueError(f"eps={eps}: must be a non-negative finite number")
+    on_device("lnp", x, alpha, beta, nb.idx, nb.ptr, nb.ent)
+    load()
+    return _LocalNormPool.apply(x, alpha.reshape(-1), beta.reshape(-1), nb, eps)
+
+
+class _KNorm(nn.Module):
+    """The parameters of the reference's K_Norm under its names (`lga.affine_alpha_feat`, `lga.affine_beta_feat`, [1, 1, 1, 2C])."""
+
+    def __init__(self, out_dim, k_group_size):
+        super().__init__()
+        self.k_group_size = k_group_size
+        self.affine_alpha_feat = nn.Parameter(torch.ones([1, 1, 1, out_dim]))
+        self.affine_beta_feat = nn.Parameter(torch.zeros([1, 1, 1, out_dim]))
+
+
+class _PostShareMLP(nn.Module):
+    """The reference's Post_ShareMLP (`mlp.share_mlp`, a 1x1 Conv1d); LNPBlock applies its weight as a linear map on (B, G, 2C)."""
+
+    def __init__(self, in_dim, out_dim):
+        super().__init__()
+        self.share_mlp = nn.Conv1d(in_dim, out_dim, 1)
+
+
+class LNPBlock(nn.Module):
+    """The reference's LNPBlock (Mamba3D.py:305-354) with its constructor and its parameter names, so its state_dict loads unchanged.
+    forward(center, feat, neighbours=None): feat (B, G+1, C) with the cls token first, which passes through; center (B, G, 3).  Pass the
+    result of lnp.neighbours(center, k_group_size) to share one search among the blocks of a forward; None runs it here."""
+
+    def __init__(self, lga_out_dim, k_group_size, alpha, beta, mlp_in_dim, mlp_out_dim, num_group=128, act_layer=nn.SiLU,
+                 drop_path=0.0, norm_layer=nn.LayerNorm):
+        super().__init__()
+        self.num_group = num_group
+        self.lga_out_dim = lga_out_dim
+        self.lga = _KNorm(lga_out_dim, k_group_size)
+        self.mlp = _PostShareMLP(mlp_in_dim, mlp_out_dim)
+        self.pre_norm_ft = norm_layer(lga_out_dim)
+        self.act = act_layer()
+
+    def forward(self, center, feat, neighbours=None):
+        nb = _search(center, self.lga.k_group_size) if neighbours is None else neighbours
+        pooled = local_norm_pool(feat[:, 1:, :], nb, self.lga.affine_alpha_feat, self.lga.affine_beta_feat)
+        conv = self.mlp.share_mlp
+        y = self.act(F.linear(self.pre_norm_ft(pooled), conv.weight.squeeze(-1), conv.bias))
+        return torch.cat((feat[:, :1, :], y), dim=1)
