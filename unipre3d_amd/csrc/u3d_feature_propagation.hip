@@ -9,11 +9,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "u3d_group.h"
 #include "u3d_knn_core.h"
 #include "u3d_util.h"
 #include "unipre3d_feature_propagation.h"
 
 namespace {
+
+using u3d_util::bad_ptr;
 
 constexpr int TILE = U3D_FEATURE_PROPAGATION_TILE;   // support points staged per pass of the search (12 KB of LDS)
 constexpr int SEARCH_NT = 128;                       // queries per workgroup of the search
@@ -110,53 +113,22 @@ __global__ __launch_bounds__(FWD_NT) void fp_fwd_kernel(const int32_t* __restric
   }
 }
 
-// ---- inverse lists --------------------------------------------------------------------------------------------------------------
-// list of entry e: the support point it names, or S (the list of the entries that name none)
-__device__ __forceinline__ int list_target(const int32_t* idx_b, int e, int S) {
-  const int v = idx_b[e];
-  return ((unsigned)v < (unsigned)S) ? v : S;
-}
-
-// counts into ptr_b[1 ..], an inclusive scan in place, then every entry dropped at an atomic cursor (the order inside a list is arbitrary
-// here; fp_list_sort_kernel ranks it).  One workgroup per batch element, phases separated by a device-scope fence and a barrier.
+// ---- inverse lists (u3d_group.h) ------------------------------------------------------------------------------------------------
+// One workgroup per batch element.  List of entry e: the support point it names, or S, the overflow list of the entries that name none.
 __global__ __launch_bounds__(LIST_NT) void fp_list_build_kernel(const int32_t* __restrict__ idx, int32_t* ptr, int32_t* cur, int32_t* tmp,
                                                                 int N, int S) {
   __shared__ uint32_t wt[LIST_WAVES];
   const size_t b = blockIdx.x;
   const int n3 = 3 * N;
   const int32_t* idx_b = idx + b * n3;
-  int32_t* ptr_b = ptr + b * (S + 1);
-  int32_t* cur_b = cur + b * (S + 1);
-  int32_t* tmp_b = tmp + b * n3;
-  for (int j = threadIdx.x; j <= S; j += LIST_NT) ptr_b[j] = 0;
-  __threadfence();
-  __syncthreads();
-  for (int e = threadIdx.x; e < n3; e += LIST_NT) {
-    const int t = list_target(idx_b, e, S);
-    if (t < S) atomicAdd(&ptr_b[t + 1], 1);
-  }
-  __threadfence();
-  __syncthreads();
-  const int per = (S + 1 + LIST_NT - 1) / LIST_NT;
-  const int lo = min((int)threadIdx.x * per, S + 1), hi = min(lo + per, S + 1);
-  uint32_t sum = 0;
-  for (int i = lo; i < hi; ++i) sum += (uint32_t)__hip_atomic_load(&ptr_b[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  uint32_t all;
-  uint32_t run = u3d_util::block_excl_scan<LIST_WAVES>(sum, wt, all);
-  for (int i = lo; i < hi; ++i) {
-    run += (uint32_t)__hip_atomic_load(&ptr_b[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ptr_b[i] = (int32_t)run;
-    cur_b[i] = (int32_t)run;                         // cur_b[S]: where the entries that name no support point start
-  }
-  __threadfence();
-  __syncthreads();
-  for (int e = threadIdx.x; e < n3; e += LIST_NT) {
-    const int pos = atomicAdd(&cur_b[list_target(idx_b, e, S)], 1);
-    if ((unsigned)pos < (unsigned)n3) tmp_b[pos] = e;
-  }
+  const auto target = [idx_b, S](int e) {
+    const int v = idx_b[e];
+    return ((unsigned)v < (unsigned)S) ? v : S;
+  };
+  u3d_group::build_lists<LIST_NT, LIST_WAVES, true>(target, n3, S, ptr + b * (S + 1), cur + b * (S + 1), tmp + b * n3, wt);
 }
 
-// a list's entries are distinct: entry x goes to the place (number of smaller entries).  One wave per list; list S ends at 3N.
+// One wave per list; list S ends at 3N.
 __global__ __launch_bounds__(SORT_NT) void fp_list_sort_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ tmp,
                                                                int32_t* __restrict__ ent, int N, int S, long long rows) {
   const uint32_t lane = u3d_util::lane_id();
@@ -165,18 +137,8 @@ __global__ __launch_bounds__(SORT_NT) void fp_list_sort_kernel(const int32_t* __
   const long long b = row / (S + 1);
   const int s = (int)(row % (S + 1)), n3 = 3 * N;
   const int32_t* pb = ptr + b * (S + 1);
-  const int32_t* src = tmp + b * n3;
-  int32_t* dst = ent + b * n3;
   const int p0 = max(0, min(pb[s], n3)), p1 = s < S ? max(p0, min(pb[s + 1], n3)) : n3;
-  for (int i0 = p0; i0 < p1; i0 += 64) {
-    const int i = i0 + (int)lane;
-    if (i < p1) {
-      const int x = src[i];
-      int rank = 0;
-      for (int q = p0; q < p1; ++q) rank += src[q] < x ? 1 : 0;
-      dst[p0 + rank] = x;
-    }
-  }
+  u3d_group::rank_list(tmp + b * n3, ent + b * n3, p0, p1, lane);
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------------------
@@ -239,7 +201,6 @@ int plan_channels(int D1, int D2) {
   if (D1 < 0 || D2 < 1) return 1;
   return (D1 > U3D_FEATURE_PROPAGATION_MAX_CHANNELS || D2 > U3D_FEATURE_PROPAGATION_MAX_CHANNELS) ? 2 : 0;
 }
-bool bad(const void* p) { return p == nullptr || !u3d_util::aligned16(p); }
 
 }  // namespace
 
@@ -253,7 +214,7 @@ size_t u3d_feature_propagation_scratch_bytes(int B, int N, int S) {
 }
 
 int u3d_feature_propagation_search(const float* xyz1, const float* xyz2, int32_t* idx, float* weight, int B, int N, int S, void* stream) {
-  if (bad(xyz1) || bad(xyz2) || bad(idx) || bad(weight)) return 1;
+  if (bad_ptr(xyz1) || bad_ptr(xyz2) || bad_ptr(idx) || bad_ptr(weight)) return 1;
   if (const int rc = plan(B, N, S)) return rc;
   const int nblk = u3d_util::blocks(N, SEARCH_NT);
   hipLaunchKernelGGL(fp_search_kernel, dim3(B * nblk), dim3(SEARCH_NT), 0, (hipStream_t)stream, xyz1, xyz2, idx, weight, N, S, nblk);
@@ -261,7 +222,7 @@ int u3d_feature_propagation_search(const float* xyz1, const float* xyz2, int32_t
 }
 
 int u3d_feature_propagation_lists(const int32_t* idx, int32_t* ptr, int32_t* ent, void* scratch, int B, int N, int S, void* stream) {
-  if (bad(idx) || bad(ptr) || bad(ent) || bad(scratch)) return 1;
+  if (bad_ptr(idx) || bad_ptr(ptr) || bad_ptr(ent) || bad_ptr(scratch)) return 1;
   if (const int rc = plan(B, N, S)) return rc;
   int32_t* cur = static_cast<int32_t*>(scratch);
   int32_t* tmp = cur + (size_t)B * (S + 1);
@@ -275,9 +236,9 @@ int u3d_feature_propagation_lists(const int32_t* idx, int32_t* ptr, int32_t* ent
 
 int u3d_feature_propagation_fwd(const int32_t* idx, const float* weight, const float* points1, const float* points2, float* out, int B,
                                 int N, int S, int D1, int D2, void* stream) {
-  if (bad(idx) || bad(weight) || bad(points2) || bad(out)) return 1;
+  if (bad_ptr(idx) || bad_ptr(weight) || bad_ptr(points2) || bad_ptr(out)) return 1;
   if (const int rc = plan_channels(D1, D2)) return rc;
-  if (D1 > 0 ? bad(points1) : (points1 != nullptr && !u3d_util::aligned16(points1))) return 1;
+  if (D1 > 0 ? bad_ptr(points1) : (points1 != nullptr && !u3d_util::aligned16(points1))) return 1;
   if (const int rc = plan(B, N, S)) return rc;
   const int nblk = u3d_util::blocks(N, FWD_NT);
   hipLaunchKernelGGL(fp_fwd_kernel, dim3(B * nblk, u3d_util::blocks(D1 + D2, FWD_CT)), dim3(FWD_NT), 0, (hipStream_t)stream, idx, weight,
@@ -287,7 +248,7 @@ int u3d_feature_propagation_fwd(const int32_t* idx, const float* weight, const f
 
 int u3d_feature_propagation_bwd(const int32_t* ptr, const int32_t* ent, const float* weight, const float* dout, float* dpoints2, int B,
                                 int N, int S, int D1, int D2, void* stream) {
-  if (bad(ptr) || bad(ent) || bad(weight) || bad(dout) || bad(dpoints2)) return 1;
+  if (bad_ptr(ptr) || bad_ptr(ent) || bad_ptr(weight) || bad_ptr(dout) || bad_ptr(dpoints2)) return 1;
   if (const int rc = plan_channels(D1, D2)) return rc;
   if (const int rc = plan(B, N, S)) return rc;
   const int sblk = u3d_util::blocks(S, BWD_NT);

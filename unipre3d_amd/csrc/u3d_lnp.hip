@@ -8,10 +8,16 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "u3d_group.h"
 #include "u3d_util.h"
 #include "unipre3d_lnp.h"
 
 namespace {
+
+using u3d_group::lane_value;
+using u3d_group::load_neighbours;      // (idx_row, K, g, G, lane): lane k < K has neighbour k of row g, g itself where idx is outside [0, G)
+using u3d_util::bad_ptr;
+using u3d_util::block_tree_sum;
 
 constexpr int SLOTS = 2;                         // float4 groups per lane
 constexpr int ROW_NT = 256, ROW_WAVES = 4;       // stats / forward / dx kernels: four rows per workgroup
@@ -28,36 +34,6 @@ __device__ __forceinline__ F4 ld4(const float* p) {
 }
 __device__ __forceinline__ void st4(float* p, const F4& a) { *reinterpret_cast<float4*>(p) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]); }
 __device__ __forceinline__ F4 splat(float a) { return {{a, a, a, a}}; }
-
-// lane k < K: neighbour k of row g, an index outside [0, G) replaced by g
-__device__ __forceinline__ int load_neighbours(const int32_t* idx_row, int K, int g, int G, uint32_t lane) {
-  int j = g;
-  if ((int)lane < K) {
-    const int v = idx_row[lane];
-    j = ((unsigned)v < (unsigned)G) ? v : g;
-  }
-  return j;
-}
-__device__ __forceinline__ int lane_value(int v, int k) { return __builtin_amdgcn_readlane(v, k); }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {    // one fixed order; the total in every lane
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// sum of sh[0 .. NT) in a fixed tree, in every thread (sh: NT doubles of LDS)
-template <int NT>
-__device__ __forceinline__ double block_tree_sum(double mine, double* sh) {
-  sh[threadIdx.x] = mine;
-  __syncthreads();
-  for (int o = NT / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double total = sh[0];
-  __syncthreads();
-  return total;
-}
 
 // ---- inverse neighbour lists ----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NB_NT) void lnp_neighbours_kernel(const int32_t* __restrict__ idx, int32_t* __restrict__ ptr,
@@ -126,16 +102,9 @@ __global__ __launch_bounds__(ROW_NT) void lnp_stats_kernel(const float* __restri
       }
     }
   }
-  s1 = wave_sum_f64(s1);
-  s2 = wave_sum_f64(s2);
-  if (lane == 0) { sh[0][wave] = s1; sh[1][wave] = s2; }
+  u3d_group::wave_sums_to_lds<ROW_WAVES, 2>(s1, s2, sh, lane, wave);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0, b = 0.0;
-    for (int w = 0; w < ROW_WAVES; ++w) { a += sh[0][w]; b += sh[1][w]; }
-    part[2 * blockIdx.x] = a;
-    part[2 * blockIdx.x + 1] = b;
-  }
+  u3d_group::block_sums_to_part<ROW_WAVES, 2>(sh, part, 2 * blockIdx.x);
 }
 
 __global__ __launch_bounds__(ROW_NT) void lnp_fwd_kernel(const float* __restrict__ x, long long xs, const int32_t* __restrict__ idx,
@@ -148,15 +117,7 @@ __global__ __launch_bounds__(ROW_NT) void lnp_fwd_kernel(const float* __restrict
   const bool has = (int)threadIdx.x < nstat;
   const double S1 = block_tree_sum<ROW_NT>(has ? part[2 * threadIdx.x] : 0.0, sh);
   const double S2 = block_tree_sum<ROW_NT>(has ? part[2 * threadIdx.x + 1] : 0.0, sh);
-  const double var = n > 1.0 ? fmax((S2 - S1 * S1 / n) / (n - 1.0), 0.0) : 0.0;
-  const float mu = (float)(S1 / n), sd = (float)sqrt(var);
-  const float r = 1.f / (sd + eps);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    stats[0] = mu;
-    stats[1] = sd;
-    stats[2] = r;
-    stats[3] = sd > 0.f ? (float)((double)r * (double)r / ((n - 1.0) * (double)sd)) : 0.f;
-  }
+  const float r = u3d_group::norm_stats(S1, S2, n, eps, blockIdx.x, stats);
   const uint32_t lane = u3d_util::lane_id();
   const int wave = threadIdx.x >> 6, C4 = C >> 2;
   const long long row = (long long)blockIdx.x * ROW_WAVES + wave;
@@ -238,7 +199,7 @@ __global__ __launch_bounds__(BWD_NT) void lnp_bwd_partial_kernel(const float* __
                                                                  double* __restrict__ tpart, float* __restrict__ ppart, int G, int K, int C,
                                                                  long long rows, int nwg) {
   __shared__ float shp[4 * U3D_LNP_MAX_CHANNELS];      // [dalpha lower | dbeta lower | dalpha upper | dbeta upper], C each
-  __shared__ double sht[BWD_WAVES];
+  __shared__ double sht[1][BWD_WAVES];
   const uint32_t lane = u3d_util::lane_id();
   const int wave = threadIdx.x >> 6, C4 = C >> 2;
   const float r = stats[2];
@@ -292,8 +253,7 @@ __global__ __launch_bounds__(BWD_NT) void lnp_bwd_partial_kernel(const float* __
       }
     }
   }
-  t = wave_sum_f64(t);
-  if (lane == 0) sht[wave] = t;
+  u3d_group::wave_sums_to_lds<BWD_WAVES, 1>(t, 0.0, sht, lane, wave);
   // the eight waves' rows, added in wave order
   for (int w = 0; w < BWD_WAVES; ++w) {
     if (wave == w) {
@@ -316,12 +276,7 @@ __global__ __launch_bounds__(BWD_NT) void lnp_bwd_partial_kernel(const float* __
     __syncthreads();
   }
   for (int i = threadIdx.x; i < 4 * C; i += BWD_NT) ppart[(size_t)blockIdx.x * 4 * C + i] = shp[i];
-  if (threadIdx.x == 0) {
-    double a = 0.0;
-    for (int w = 0; w < BWD_WAVES; ++w) a += sht[w];
-    tpart[2 * blockIdx.x] = a;
-    tpart[2 * blockIdx.x + 1] = 0.0;
-  }
+  u3d_group::block_sums_to_part<BWD_WAVES, 1>(sht, tpart, 2 * blockIdx.x);      // (t, 0)
 }
 
 __global__ __launch_bounds__(ROW_NT) void lnp_bwd_dx_kernel(const float* __restrict__ x, long long xs, const int32_t* __restrict__ idx,
@@ -474,8 +429,6 @@ int plan(int B, int G, int K, int C, Plan& p) {
 size_t fwd_scratch(const Plan& p) { return (size_t)p.stat_wg * 2 * sizeof(double); }
 size_t bwd_scratch(const Plan& p, int C) { return (size_t)p.bwd_wg * (2 * sizeof(double) + (size_t)4 * C * sizeof(float)); }
 
-bool bad(const void* p) { return p == nullptr || !u3d_util::aligned16(p); }
-
 }  // namespace
 
 extern "C" {
@@ -489,7 +442,7 @@ size_t u3d_lnp_scratch_bytes(int B, int G, int K, int C, int backward) {
 }
 
 int u3d_lnp_neighbours(const int32_t* idx, int32_t* ptr, int32_t* ent, int B, int G, int K, void* stream) {
-  if (bad(idx) || bad(ptr) || bad(ent)) return 1;
+  if (bad_ptr(idx) || bad_ptr(ptr) || bad_ptr(ent)) return 1;
   Plan p;
   if (const int rc = plan(B, G, K, 4, p)) return rc;
   hipLaunchKernelGGL(lnp_neighbours_kernel, dim3(B), dim3(NB_NT), 0, (hipStream_t)stream, idx, ptr, ent, G, K);
@@ -498,7 +451,7 @@ int u3d_lnp_neighbours(const int32_t* idx, int32_t* ptr, int32_t* ent, int B, in
 
 int u3d_lnp_fwd(const float* x, long long x_batch_stride, const int32_t* idx, const float* alpha, const float* beta, float* out,
                 float* lse, float* stats, void* scratch, int B, int G, int K, int C, float eps, void* stream) {
-  if (bad(x) || bad(idx) || bad(alpha) || bad(beta) || bad(out) || bad(lse) || bad(stats) || bad(scratch)) return 1;
+  if (bad_ptr(x) || bad_ptr(idx) || bad_ptr(alpha) || bad_ptr(beta) || bad_ptr(out) || bad_ptr(lse) || bad_ptr(stats) || bad_ptr(scratch)) return 1;
   Plan p;
   if (const int rc = plan(B, G, K, C, p)) return rc;
   if (x_batch_stride < (long long)G * C || (x_batch_stride & 3) || !(eps >= 0.f) || !(eps < INFINITY)) return 1;
@@ -514,8 +467,8 @@ int u3d_lnp_fwd(const float* x, long long x_batch_stride, const int32_t* idx, co
 int u3d_lnp_bwd(const float* x, long long x_batch_stride, const int32_t* idx, const int32_t* ptr, const int32_t* ent,
                 const float* alpha, const float* beta, const float* out, const float* lse, const float* stats, const float* dout,
                 float* dx, float* dalpha, float* dbeta, void* scratch, int B, int G, int K, int C, void* stream) {
-  if (bad(x) || bad(idx) || bad(ptr) || bad(ent) || bad(alpha) || bad(beta) || bad(out) || bad(lse) || bad(stats) || bad(dout) ||
-      bad(dx) || bad(dalpha) || bad(dbeta) || bad(scratch))
+  if (bad_ptr(x) || bad_ptr(idx) || bad_ptr(ptr) || bad_ptr(ent) || bad_ptr(alpha) || bad_ptr(beta) || bad_ptr(out) || bad_ptr(lse) ||
+      bad_ptr(stats) || bad_ptr(dout) || bad_ptr(dx) || bad_ptr(dalpha) || bad_ptr(dbeta) || bad_ptr(scratch))
     return 1;
   Plan p;
   if (const int rc = plan(B, G, K, C, p)) return rc;

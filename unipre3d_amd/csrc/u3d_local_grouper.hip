@@ -10,10 +10,16 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "u3d_group.h"
 #include "u3d_util.h"
 #include "unipre3d_local_grouper.h"
 
 namespace {
+
+using u3d_group::lane_value;
+using u3d_group::load_neighbours;      // (idx_row, K, a, N, lane): lane k < K has neighbour k of row s, the anchor a where idx is outside [0, N)
+using u3d_util::bad_ptr;
+using u3d_util::block_tree_sum;
 
 constexpr int ROW_NT = 256, ROW_WAVES = 4;       // stats / forward / dpoints kernels: four rows per workgroup
 constexpr int STAT_MAX_WG = 128;                 // per batch element: partials of (sum d, sum d^2), one double2 per workgroup
@@ -41,94 +47,31 @@ __device__ __forceinline__ int fps_of(const int32_t* fps_b, int s, int N) {     
   const int v = fps_b[s];
   return ((unsigned)v < (unsigned)N) ? v : s;
 }
-// lane k < K: neighbour k of row s, an index outside [0, N) replaced by the anchor a
-__device__ __forceinline__ int load_neighbours(const int32_t* idx_row, int K, int a, int N, uint32_t lane) {
-  int j = a;
-  if ((int)lane < K) {
-    const int v = idx_row[lane];
-    j = ((unsigned)v < (unsigned)N) ? v : a;
+
+// ---- inverse lists (u3d_group.h) ------------------------------------------------------------------------------------------------
+// target of entry e of a table with K entries per anchor: what it names, or the anchor (tab == nullptr: the identity fps)
+struct ListTarget {
+  const int32_t* tab;
+  const int32_t* fps_b;
+  int K, N;
+  __device__ __forceinline__ int operator()(int e) const {
+    const int v = tab != nullptr ? tab[e] : -1;
+    return ((unsigned)v < (unsigned)N) ? v : fps_of(fps_b, e / K, N);
   }
-  return j;
-}
-__device__ __forceinline__ int lane_value(int v, int k) { return __builtin_amdgcn_readlane(v, k); }
+};
 
-__device__ __forceinline__ double wave_sum_f64(double v) {    // one fixed order; the total in every lane
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-template <int NT>
-__device__ __forceinline__ double block_tree_sum(double mine, double* sh) {     // sh: NT doubles of LDS; the total in every thread
-  sh[threadIdx.x] = mine;
-  __syncthreads();
-  for (int o = NT / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-    __syncthreads();
-  }
-  const double total = sh[0];
-  __syncthreads();
-  return total;
-}
-
-// ---- inverse lists --------------------------------------------------------------------------------------------------------------
-// target of entry e of a table of n entries, K per anchor (tab == nullptr: the identity fps)
-__device__ __forceinline__ int list_target(const int32_t* tab, const int32_t* fps_b, int e, int K, int N) {
-  const int v = tab != nullptr ? tab[e] : -1;
-  return ((unsigned)v < (unsigned)N) ? v : fps_of(fps_b, e / K, N);
-}
-
-// counts into ptr_b[1 ..], an inclusive scan in place, then every entry dropped at an atomic cursor (the order inside a list is arbitrary
-// here; lg_list_sort_kernel ranks it).  All of it by one workgroup, phases separated by a device-scope fence and a barrier.
-__device__ void list_build(const int32_t* tab, const int32_t* fps_b, int n, int K, int N, int32_t* ptr_b, int32_t* cur_b, int32_t* tmp_b,
-                           uint32_t* wt) {
-  for (int j = threadIdx.x; j <= N; j += LIST_NT) ptr_b[j] = 0;
-  __threadfence();
-  __syncthreads();
-  for (int e = threadIdx.x; e < n; e += LIST_NT) atomicAdd(&ptr_b[list_target(tab, fps_b, e, K, N) + 1], 1);
-  __threadfence();
-  __syncthreads();
-  const int per = (N + 1 + LIST_NT - 1) / LIST_NT;
-  const int lo = min((int)threadIdx.x * per, N + 1), hi = min(lo + per, N + 1);
-  uint32_t sum = 0;
-  for (int i = lo; i < hi; ++i) sum += (uint32_t)__hip_atomic_load(&ptr_b[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  uint32_t all;
-  uint32_t run = u3d_util::block_excl_scan<LIST_WAVES>(sum, wt, all);
-  for (int i = lo; i < hi; ++i) {
-    run += (uint32_t)__hip_atomic_load(&ptr_b[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ptr_b[i] = (int32_t)run;
-    if (i < N) cur_b[i] = (int32_t)run;
-  }
-  __threadfence();
-  __syncthreads();
-  for (int e = threadIdx.x; e < n; e += LIST_NT) {
-    const int pos = atomicAdd(&cur_b[list_target(tab, fps_b, e, K, N)], 1);
-    if ((unsigned)pos < (unsigned)n) tmp_b[pos] = e;
-  }
-  __threadfence();
-  __syncthreads();
-}
-
+// both tables of a batch element by one workgroup: the neighbours', then the anchors' with the same cursors and scan words
 __global__ __launch_bounds__(LIST_NT) void lg_list_build_kernel(const int32_t* __restrict__ fps, const int32_t* __restrict__ idx,
                                                                 int32_t* ptr, int32_t* fptr, int32_t* cur, int32_t* tmpe, int32_t* tmpf,
                                                                 int N, int S, int K) {
   __shared__ uint32_t wt[LIST_WAVES];
   const size_t b = blockIdx.x;
   const int32_t* fps_b = fps != nullptr ? fps + b * S : nullptr;
-  list_build(idx + b * S * K, fps_b, S * K, K, N, ptr + b * (N + 1), cur + b * N, tmpe + b * S * K, wt);
-  list_build(fps_b, fps_b, S, 1, N, fptr + b * (N + 1), cur + b * N, tmpf + b * S, wt);
-}
-
-// a list's entries are distinct: entry x goes to the place (number of smaller entries)
-__device__ __forceinline__ void list_rank(const int32_t* __restrict__ tmp, int32_t* __restrict__ dst, int p0, int p1, uint32_t lane) {
-  for (int i0 = p0; i0 < p1; i0 += 64) {
-    const int i = i0 + (int)lane;
-    if (i < p1) {
-      const int x = tmp[i];
-      int rank = 0;
-      for (int q = p0; q < p1; ++q) rank += tmp[q] < x ? 1 : 0;
-      dst[p0 + rank] = x;
-    }
-  }
+  u3d_group::build_lists<LIST_NT, LIST_WAVES, false>(ListTarget{idx + b * S * K, fps_b, K, N}, S * K, N, ptr + b * (N + 1), cur + b * N,
+                                                     tmpe + b * S * K, wt);
+  __threadfence();
+  __syncthreads();
+  u3d_group::build_lists<LIST_NT, LIST_WAVES, false>(ListTarget{fps_b, fps_b, 1, N}, S, N, fptr + b * (N + 1), cur + b * N, tmpf + b * S, wt);
 }
 
 __global__ __launch_bounds__(ROW_NT) void lg_list_sort_kernel(const int32_t* __restrict__ ptr, const int32_t* __restrict__ fptr,
@@ -143,9 +86,9 @@ __global__ __launch_bounds__(ROW_NT) void lg_list_sort_kernel(const int32_t* __r
   const int32_t* pb = ptr + b * (N + 1);
   const int32_t* fb = fptr + b * (N + 1);
   const int e0 = max(0, min(pb[j], n)), e1 = max(e0, min(pb[j + 1], n));
-  list_rank(tmpe + b * n, ent + b * n, e0, e1, lane);
+  u3d_group::rank_list(tmpe + b * n, ent + b * n, e0, e1, lane);
   const int f0 = max(0, min(fb[j], S)), f1 = max(f0, min(fb[j + 1], S));
-  list_rank(tmpf + b * S, fent + b * S, f0, f1, lane);
+  u3d_group::rank_list(tmpf + b * S, fent + b * S, f0, f1, lane);
 }
 
 // ---- forward --------------------------------------------------------------------------------------------------------------------
@@ -195,16 +138,9 @@ __global__ __launch_bounds__(ROW_NT) void lg_stats_kernel(const float* __restric
       }
     }
   }
-  s1 = wave_sum_f64(s1);
-  s2 = wave_sum_f64(s2);
-  if (lane == 0) { sh[0][wave] = s1; sh[1][wave] = s2; }
+  u3d_group::wave_sums_to_lds<ROW_WAVES, 2>(s1, s2, sh, lane, wave);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double x = 0.0, y = 0.0;
-    for (int i = 0; i < ROW_WAVES; ++i) { x += sh[0][i]; y += sh[1][i]; }
-    part[2 * (size_t)blockIdx.x] = x;
-    part[2 * (size_t)blockIdx.x + 1] = y;
-  }
+  u3d_group::block_sums_to_part<ROW_WAVES, 2>(sh, part, 2 * (size_t)blockIdx.x);
 }
 
 __global__ __launch_bounds__(ROW_NT) void lg_fwd_kernel(const float* __restrict__ xyz, const float* __restrict__ points, long long pb,
@@ -225,15 +161,7 @@ __global__ __launch_bounds__(ROW_NT) void lg_fwd_kernel(const float* __restrict_
     const double S1 = block_tree_sum<ROW_NT>(has ? pt[2 * threadIdx.x] : 0.0, sh);
     const double S2 = block_tree_sum<ROW_NT>(has ? pt[2 * threadIdx.x + 1] : 0.0, sh);
     const double n = (double)dm.S * dm.K * dm.Cn;
-    const double var = n > 1.0 ? fmax((S2 - S1 * S1 / n) / (n - 1.0), 0.0) : 0.0;
-    const float mu = (float)(S1 / n), sd = (float)sqrt(var);
-    r = 1.f / (sd + eps);
-    if (blk == 0 && threadIdx.x == 0) {
-      stats[4 * b] = mu;
-      stats[4 * b + 1] = sd;
-      stats[4 * b + 2] = r;
-      stats[4 * b + 3] = sd > 0.f ? (float)((double)r * (double)r / ((n - 1.0) * (double)sd)) : 0.f;
-    }
+    r = u3d_group::norm_stats(S1, S2, n, eps, blk, stats + 4 * b);
   }
   const uint32_t lane = u3d_util::lane_id();
   const int s = blk * ROW_WAVES + (int)(threadIdx.x >> 6);
@@ -275,7 +203,7 @@ __global__ __launch_bounds__(BWD_NT) void lg_bwd_partial_kernel(const float* __r
                                                                 float* __restrict__ ppart, float* __restrict__ gysum, float* __restrict__ dsum,
                                                                 float* __restrict__ gasum, Dims dm, int normalize, int dcf, int nwg) {
   __shared__ float shp[2 * MAX_CN];      // [dalpha | dbeta], Cn each
-  __shared__ double sht[BWD_WAVES];
+  __shared__ double sht[1][BWD_WAVES];
   const uint32_t lane = u3d_util::lane_id();
   const int wave = threadIdx.x >> 6;
   const size_t b = blockIdx.x / nwg;
@@ -331,8 +259,7 @@ __global__ __launch_bounds__(BWD_NT) void lg_bwd_partial_kernel(const float* __r
     }
   }
   if (!norm) return;
-  t = wave_sum_f64(t);
-  if (lane == 0) sht[wave] = t;
+  u3d_group::wave_sums_to_lds<BWD_WAVES, 1>(t, 0.0, sht, lane, wave);
   // the eight waves' rows, added in wave order
   for (int wv = 0; wv < BWD_WAVES; ++wv) {
     if (wave == wv) {
@@ -348,12 +275,7 @@ __global__ __launch_bounds__(BWD_NT) void lg_bwd_partial_kernel(const float* __r
     __syncthreads();
   }
   for (int i = threadIdx.x; i < 2 * dm.Cn; i += BWD_NT) ppart[(size_t)blockIdx.x * 2 * dm.Cn + i] = shp[i];
-  if (threadIdx.x == 0) {
-    double x = 0.0;
-    for (int i = 0; i < BWD_WAVES; ++i) x += sht[i];
-    tpart[2 * (size_t)blockIdx.x] = x;
-    tpart[2 * (size_t)blockIdx.x + 1] = 0.0;
-  }
+  u3d_group::block_sums_to_part<BWD_WAVES, 1>(sht, tpart, 2 * (size_t)blockIdx.x);      // (T_b's part, 0)
 }
 
 __global__ __launch_bounds__(ROW_NT) void lg_bwd_dpoints_kernel(const float* __restrict__ points, long long pb, long long pp, long long pc,
@@ -497,7 +419,6 @@ size_t bwd_scratch(const Plan& p, int B, int normalize) {
 }
 size_t list_scratch(const Plan& p) { return ((size_t)p.rows_n + (size_t)p.rows_s * p.dm.K + (size_t)p.rows_s) * sizeof(int32_t); }
 
-bool bad(const void* p) { return p == nullptr || !u3d_util::aligned16(p); }
 bool bad_strides(long long sb, long long sp, long long sc, int N, int D) {
   return !((sp == D && sc == 1) || (sp == 1 && sc == N)) || sb < (long long)N * D;
 }
@@ -516,7 +437,9 @@ size_t u3d_local_grouper_scratch_bytes(int B, int N, int S, int K, int D, int us
 
 int u3d_local_grouper_lists(const int32_t* fps, const int32_t* idx, int32_t* ptr, int32_t* ent, int32_t* fptr, int32_t* fent, void* scratch,
                             int B, int N, int S, int K, void* stream) {
-  if ((fps != nullptr && !u3d_util::aligned16(fps)) || bad(idx) || bad(ptr) || bad(ent) || bad(fptr) || bad(fent) || bad(scratch)) return 1;
+  if ((fps != nullptr && !u3d_util::aligned16(fps)) || bad_ptr(idx) || bad_ptr(ptr) || bad_ptr(ent) || bad_ptr(fptr) || bad_ptr(fent) ||
+      bad_ptr(scratch))
+    return 1;
   Plan p;
   if (const int rc = plan(B, N, S, K, 4, 0, NORM_NONE, p)) return rc;
   if (fps == nullptr && S != N) return 1;
@@ -534,10 +457,10 @@ int u3d_local_grouper_fwd(const float* xyz, const float* points, long long p_bat
                           const int32_t* idx, const float* alpha, const float* beta, float* out, float* new_xyz, float* mean, float* stats,
                           void* scratch, int B, int N, int S, int K, int D, int use_xyz, int normalize, int channels_first, float eps,
                           void* stream) {
-  if (bad(xyz) || bad(points) || (fps != nullptr && !u3d_util::aligned16(fps)) || bad(idx) || bad(out) || bad(new_xyz)) return 1;
+  if (bad_ptr(xyz) || bad_ptr(points) || (fps != nullptr && !u3d_util::aligned16(fps)) || bad_ptr(idx) || bad_ptr(out) || bad_ptr(new_xyz)) return 1;
   Plan p;
   if (const int rc = plan(B, N, S, K, D, use_xyz, normalize, p)) return rc;
-  if (normalize != NORM_NONE && (bad(alpha) || bad(beta) || bad(mean) || bad(stats) || bad(scratch))) return 1;
+  if (normalize != NORM_NONE && (bad_ptr(alpha) || bad_ptr(beta) || bad_ptr(mean) || bad_ptr(stats) || bad_ptr(scratch))) return 1;
   if (bad_strides(p_batch, p_point, p_chan, N, D) || (channels_first != 0 && channels_first != 1) || (fps == nullptr && S != N) ||
       !(eps >= 0.f) || !(eps < INFINITY))
     return 1;
@@ -557,12 +480,12 @@ int u3d_local_grouper_bwd(const float* xyz, const float* points, long long p_bat
                           const float* alpha, const float* mean, const float* stats, const float* dout, float* dpoints, long long g_batch,
                           long long g_point, long long g_chan, float* dalpha, float* dbeta, void* scratch, int B, int N, int S, int K, int D,
                           int use_xyz, int normalize, int dout_channels_first, void* stream) {
-  if (bad(xyz) || bad(points) || (fps != nullptr && !u3d_util::aligned16(fps)) || bad(idx) || bad(ptr) || bad(ent) || bad(fptr) ||
-      bad(fent) || bad(dout) || bad(dpoints) || bad(scratch))
+  if (bad_ptr(xyz) || bad_ptr(points) || (fps != nullptr && !u3d_util::aligned16(fps)) || bad_ptr(idx) || bad_ptr(ptr) || bad_ptr(ent) ||
+      bad_ptr(fptr) || bad_ptr(fent) || bad_ptr(dout) || bad_ptr(dpoints) || bad_ptr(scratch))
     return 1;
   Plan p;
   if (const int rc = plan(B, N, S, K, D, use_xyz, normalize, p)) return rc;
-  if (normalize != NORM_NONE && (bad(alpha) || bad(mean) || bad(stats) || bad(dalpha) || bad(dbeta))) return 1;
+  if (normalize != NORM_NONE && (bad_ptr(alpha) || bad_ptr(mean) || bad_ptr(stats) || bad_ptr(dalpha) || bad_ptr(dbeta))) return 1;
   if (bad_strides(p_batch, p_point, p_chan, N, D) || bad_strides(g_batch, g_point, g_chan, N, D) ||
       (dout_channels_first != 0 && dout_channels_first != 1) || (fps == nullptr && S != N))
     return 1;

@@ -18,6 +18,7 @@ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int launched() { return hipGetLastError() == hipSuccess ? 0 : 3; }
 U3D_UTIL_HD inline int blocks(long long n, int per) { return (int)((n + per - 1) / per); }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+inline bool bad_ptr(const void* p) { return p == nullptr || !aligned16(p); }      // what an entry point refuses for a required buffer
 // steps a lane owns in one 64-lane pass over a row of length L (the selective scan's passes, the causal conv's chunks)
 inline int steps_per_lane(int L) { return L <= 64 ? 1 : L <= 128 ? 2 : L <= 192 ? 3 : 4; }
 
@@ -56,6 +57,23 @@ __device__ __forceinline__ float wave_sum(float v) {              // the sum of 
   v += dpp_f<0x142, 0xa>(0.f, v);   // row_bcast:15 into rows 1 and 3
   v += dpp_f<0x143, 0xc>(0.f, v);   // row_bcast:31 into rows 2 and 3
   return lane_f<63>(v);
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {       // one fixed order; the total in every lane
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+// sum of the NT threads' `mine` in a fixed tree, in every thread (sh: NT doubles of LDS)
+template <int NT>
+__device__ __forceinline__ double block_tree_sum(double mine, double* sh) {
+  sh[threadIdx.x] = mine;
+  __syncthreads();
+  for (int o = NT / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  const double total = sh[0];
+  __syncthreads();
+  return total;
 }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 #endif
