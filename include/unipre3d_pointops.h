@@ -9,8 +9,9 @@
  *
  *   u3d_furthest_point_sampling  <- furthest_point_sampling_wrapper(b, n, m, points (B,N,3), temp (B,N), idx (B,M))
  *        Start index 0; ties in the arg-max resolve exactly as the reference's block reduction does for its block size
- *        opt_n_threads(n) (cuda_utils.h:10-14), see oracle/pointops_oracle.c.  `temp` is unused scratch kept for
- *        signature parity (may be NULL): minimum distances live in registers.
+ *        opt_n_threads(n) (cuda_utils.h:10-14), see oracle/pointops_oracle.c.  Up to 8192 points `temp` is unused, kept for
+ *        signature parity (may be NULL): minimum distances live in registers.  Above 8192 points it is required (NULL: returns 1)
+ *        and every element of it is written: the running minimum distances.
  *   u3d_ball_query               <- ball_query_wrapper(b, n, m, radius, nsample, new_xyz (B,M,3), xyz (B,N,3), idx (B,M,nsample))
  *        First `nsample` support points with d^2 < r^2 in index order, padded with the first hit; rows without any hit
  *        are written as zeros (the reference relies on the caller's zero_()).

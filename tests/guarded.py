@@ -85,6 +85,17 @@ class Arena:
             self.own(p.view, owned)
         return p.view
 
+    def scratch(self, nbytes: int, name: str = "scratch"):
+        """A uint8 placement of exactly `nbytes` bytes at a 256-byte boundary for a scratch, workspace or partials buffer: guarded like
+        any output, and simply not returned from the case, so that its bytes (which may hold anything) stay out of the bit comparison."""
+        view = self.out((int(nbytes),), torch.uint8, name=name)
+        assert self.address(view) % ALIGN == 0
+        return view
+
+    def address(self, view) -> int:
+        """Device address of a placement's first byte (an empty tensor's data_ptr() is 0; its placement still has an address)."""
+        return self.base + self.placement_of(view).start
+
     def own(self, view, rows: int):
         """Narrows the owned region of an out() placement to its first `rows` rows (for counts only known after the call) and returns that
         prefix view."""

@@ -84,6 +84,36 @@ def test_a_value_read_past_an_input_is_reported():
         run_twice(lambda arena: _clean(arena, "overread"), "cpu")
 
 
+def _with_scratch(arena, flaw=None):
+    """y = 2 x through a 100-byte scratch that ends up holding the poison's own byte + 1 (so its contents differ between the runs)"""
+    x = arena.inp(X, name="x")
+    ws = arena.scratch(100, name="ws")
+    y = arena.out(X.shape, torch.float32, name="y")
+    assert ws.dtype == torch.uint8 and ws.numel() == 100 and ws.data_ptr() % 256 == 0 and arena.address(ws) == ws.data_ptr()
+    ws.fill_((arena.poison + 1) & 0xFF)
+    y.copy_(2 * x)
+    if flaw == "past_scratch":
+        p = arena.placement_of(ws)
+        arena.buf[p.start + 100] = 7
+    return [y]
+
+
+def test_scratch_is_guarded_but_stays_out_of_the_comparison():
+    a, b = run_twice(_with_scratch, "cpu")
+    assert guarded.same_bits(a[0], 2 * X) and guarded.same_bits(b[0], 2 * X)
+    with pytest.raises(AssertionError, match=r"placement 'ws' were overwritten \(after it\): 1 bytes, first at offset 100, last at offset 100 "):
+        run_twice(lambda arena: _with_scratch(arena, "past_scratch"), "cpu")
+
+
+def test_address_of_an_empty_placement():
+    arena = Arena("cpu", 0xFF, capacity=1 << 20)
+    e = arena.out((0,), torch.float32, misalign=12, name="empty")
+    a = arena.out((3,), torch.float32, misalign=4, name="a")
+    assert e.numel() == 0 and arena.address(e) % 256 == 12 and arena.address(e) >= arena.base + 4096
+    assert arena.address(a) == a.data_ptr() and arena.address(a) - arena.address(e) >= 2 * 4096 - 12
+    arena.check_guards()
+
+
 def test_the_minus_one_a_knn_leaves_is_not_mistaken_for_poison():
     def fn(arena):
         idx = arena.out((4, 3), torch.int32, name="idx")
