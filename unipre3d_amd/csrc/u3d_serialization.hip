@@ -91,11 +91,14 @@ __global__ __launch_bounds__(NT) void encode_kernel(int n, const CT* __restrict_
 }
 
 // ---- stable LSD radix sort of (64-bit key, 32-bit index), 8 bits per pass, row = blockIdx.y ------------------------------------
-__device__ __forceinline__ uint32_t digit_of(u64 k, int shift, int pre) { return (uint32_t)((k >> pre) >> shift) & 255u; }
+// flip: 0, or 0x80 in the top pass of a SIGNED sort (the sign bit inverted puts the negative keys first)
+__device__ __forceinline__ uint32_t digit_of(u64 k, int shift, int pre, uint32_t flip = 0) {
+  return ((uint32_t)((k >> pre) >> shift) & 255u) ^ flip;
+}
 
 // hist: per row 256 x nb counts, digit-major (a scan of each digit's line gives the (digit, tile) bases), then 256 totals
-__global__ __launch_bounds__(NT) void radix_hist_kernel(int shift, int pre, int n, int nb, size_t kstride, const u64* __restrict__ kin,
-                                                        uint32_t* __restrict__ hist) {
+__global__ __launch_bounds__(NT) void radix_hist_kernel(int shift, int pre, uint32_t flip, int n, int nb, size_t kstride,
+                                                        const u64* __restrict__ kin, uint32_t* __restrict__ hist) {
   __shared__ uint32_t h[256];
   h[threadIdx.x] = 0;
   __syncthreads();
@@ -104,7 +107,7 @@ __global__ __launch_bounds__(NT) void radix_hist_kernel(int shift, int pre, int 
   const uint32_t base = blockIdx.x * (uint32_t)TILE;
   for (int r = 0; r < ITEMS; ++r) {
     const uint32_t i = base + r * NT + threadIdx.x;
-    if (i < (uint32_t)n) atomicAdd(&h[digit_of(kin[i], shift, pre)], 1u);
+    if (i < (uint32_t)n) atomicAdd(&h[digit_of(kin[i], shift, pre, flip)], 1u);
   }
   __syncthreads();
   hist[(size_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];
@@ -113,7 +116,7 @@ __global__ __launch_bounds__(NT) void radix_hist_kernel(int shift, int pre, int 
 // stable scatter of one tile: rounds of NT elements ranked by the ballot multi-split (element order = round, wave, lane).
 // FIRST: the index of an element is its position (no vin).  FINAL: writes order (the index, widened) and inverse, not (kout, vout).
 template <bool FIRST, bool FINAL>
-__global__ __launch_bounds__(NT) void radix_scatter_kernel(int shift, int pre, int n, int nb, const uint32_t* __restrict__ hist,
+__global__ __launch_bounds__(NT) void radix_scatter_kernel(int shift, int pre, uint32_t flip, int n, int nb, const uint32_t* __restrict__ hist,
                                                            size_t kstride, const u64* __restrict__ kin, const uint32_t* __restrict__ vin,
                                                            u64* __restrict__ kout, uint32_t* __restrict__ vout,
                                                            long long* __restrict__ order, long long* __restrict__ inverse) {
@@ -128,7 +131,7 @@ __global__ __launch_bounds__(NT) void radix_scatter_kernel(int shift, int pre, i
     const uint32_t i = base + r * NT + threadIdx.x;
     const bool valid = i < (uint32_t)n;
     u64 k = 0; uint32_t v = 0, digit = 0;
-    if (valid) { k = kin[i]; v = FIRST ? i : vin[row + i]; digit = digit_of(k, shift, pre); }
+    if (valid) { k = kin[i]; v = FIRST ? i : vin[row + i]; digit = digit_of(k, shift, pre, flip); }
     const uint32_t dst = radix_round_dst<NW>(lds, valid, digit);
     if (valid) {
       if (FINAL) {
@@ -144,9 +147,10 @@ __global__ __launch_bounds__(NT) void radix_scatter_kernel(int shift, int pre, i
 }
 
 // Sorts K rows of n keys (src, row stride n) on the low key_bits bits of key >> pre.  final: the last pass writes order / inverse;
-// otherwise the result is (keys[b], vals[b]) with b the returned buffer.  Keys move unshifted.
+// otherwise the result is (keys[b], vals[b]) with b the returned buffer.  Keys move unshifted.  is_signed: the keys are int64 and all
+// 64 bits are sorted, the top pass with the sign bit inverted.
 int radix_sort(const Scratch& s, int K, int n, int key_bits, int pre, const u64* src, bool final, long long* order, long long* inverse,
-               hipStream_t st) {
+               hipStream_t st, bool is_signed = false) {
   const int nb = blocks(n, TILE), passes = (key_bits + 7) / 8;
   const dim3 gt(nb, K), gs(256, K);
   const size_t ks = (size_t)n;
@@ -156,16 +160,17 @@ int radix_sort(const Scratch& s, int K, int n, int key_bits, int pre, const u64*
     u64* kout = s.keys[p & 1];
     uint32_t* vout = s.vals[p & 1];
     const bool last = final && p == passes - 1;
-    radix_hist_kernel<<<gt, NT, 0, st>>>(8 * p, pre, n, nb, ks, kin, s.hist);
+    const uint32_t flip = (is_signed && p == 7) ? 0x80u : 0u;
+    radix_hist_kernel<<<gt, NT, 0, st>>>(8 * p, pre, flip, n, nb, ks, kin, s.hist);
     digit_scan_kernel<NT><<<gs, NT, 0, st>>>(nb, s.hist);
     if (p == 0 && last)
-      radix_scatter_kernel<true, true><<<gt, NT, 0, st>>>(8 * p, pre, n, nb, s.hist, ks, kin, vin, kout, vout, order, inverse);
+      radix_scatter_kernel<true, true><<<gt, NT, 0, st>>>(8 * p, pre, flip, n, nb, s.hist, ks, kin, vin, kout, vout, order, inverse);
     else if (p == 0)
-      radix_scatter_kernel<true, false><<<gt, NT, 0, st>>>(8 * p, pre, n, nb, s.hist, ks, kin, vin, kout, vout, order, inverse);
+      radix_scatter_kernel<true, false><<<gt, NT, 0, st>>>(8 * p, pre, flip, n, nb, s.hist, ks, kin, vin, kout, vout, order, inverse);
     else if (last)
-      radix_scatter_kernel<false, true><<<gt, NT, 0, st>>>(8 * p, pre, n, nb, s.hist, ks, kin, vin, kout, vout, order, inverse);
+      radix_scatter_kernel<false, true><<<gt, NT, 0, st>>>(8 * p, pre, flip, n, nb, s.hist, ks, kin, vin, kout, vout, order, inverse);
     else
-      radix_scatter_kernel<false, false><<<gt, NT, 0, st>>>(8 * p, pre, n, nb, s.hist, ks, kin, vin, kout, vout, order, inverse);
+      radix_scatter_kernel<false, false><<<gt, NT, 0, st>>>(8 * p, pre, flip, n, nb, s.hist, ks, kin, vin, kout, vout, order, inverse);
   }
   return (passes - 1) & 1;
 }
@@ -235,6 +240,193 @@ __global__ __launch_bounds__(NT) void pool_emit_kernel(int K, int n, int M, int 
 }
 
 bool bad_shape(int K, int N) { return K < 1 || K > 4 || N < 1; }
+
+// ---- PCM's order serialization ---------------------------------------------------------------------------------------------------
+// meta: words 0..2 the global maxima of the grid per axis, 3 the depth, 4 the flag, 5..7 zero, then three maxima per item.
+constexpr int META_HEAD = U3D_SER_PCM_META_HEAD;
+constexpr int SMALL_SORT = U3D_SER_SMALL_SORT;   // most keys the one-workgroup sort takes
+
+struct I3 { long long v[3]; };
+
+// min (IS_MIN) or max over the NT threads of three values, in every thread
+template <bool IS_MIN>
+__device__ __forceinline__ I3 block_reduce3(I3 x, long long (*sh)[3]) {
+  for (int a = 0; a < 3; ++a)
+    for (int o = 32; o > 0; o >>= 1) {
+      const long long y = __shfl_xor(x.v[a], o);
+      x.v[a] = IS_MIN ? (y < x.v[a] ? y : x.v[a]) : (y > x.v[a] ? y : x.v[a]);
+    }
+  if (lane_id() == 0) for (int a = 0; a < 3; ++a) sh[threadIdx.x >> 6][a] = x.v[a];
+  __syncthreads();
+  for (int a = 0; a < 3; ++a) {
+    long long r = sh[0][a];
+    for (int w = 1; w < NW; ++w) r = IS_MIN ? (sh[w][a] < r ? sh[w][a] : r) : (sh[w][a] > r ? sh[w][a] : r);
+    x.v[a] = r;
+  }
+  __syncthreads();
+  return x;
+}
+
+// floor(p / grid_size) as the reference's int64; the division is IEEE (no fast reciprocal).  A quotient that is not finite or does not
+// fit raises `bad` and counts as cell 0.
+__device__ __forceinline__ long long cell_of(float p, float grid_size, bool& bad) {
+  const float q = floorf(p / grid_size);
+  if (!(fabsf(q) < 4.0e18f)) { bad = true; return 0; }
+  return (long long)q;
+}
+
+// one workgroup per item: the item's minimum cell, then grid = cell - minimum and the item's maxima of it (meta's tail).  A relative
+// cell above 65535 is stored clamped to 2^30 and reaches the flag through the maxima; word 0 of an item's maxima carries `bad` in bit 31.
+__global__ __launch_bounds__(NT) void pcm_grid_kernel(int N, float grid_size, const float* __restrict__ pos, int32_t* __restrict__ grid,
+                                                      int32_t* __restrict__ meta) {
+  __shared__ long long sh[NW][3];
+  const size_t row0 = (size_t)blockIdx.x * N;
+  bool bad = false;
+  I3 lo{{INT64_MAX, INT64_MAX, INT64_MAX}};
+  for (int i = threadIdx.x; i < N; i += NT)
+    for (int a = 0; a < 3; ++a) {
+      const long long c = cell_of(pos[(row0 + i) * 3 + a], grid_size, bad);
+      lo.v[a] = c < lo.v[a] ? c : lo.v[a];
+    }
+  lo = block_reduce3<true>(lo, sh);
+  I3 hi{{0, 0, 0}};
+  for (int i = threadIdx.x; i < N; i += NT)
+    for (int a = 0; a < 3; ++a) {
+      long long c = cell_of(pos[(row0 + i) * 3 + a], grid_size, bad) - lo.v[a];
+      if (c < 0) c = 0;                       // only after `bad`
+      if (c > (1ll << 30)) c = 1ll << 30;
+      grid[(row0 + i) * 3 + a] = (int32_t)c;
+      hi.v[a] = c > hi.v[a] ? c : hi.v[a];
+    }
+  hi.v[0] |= bad ? (1ll << 31) : 0;           // above every clamped cell: survives the maximum
+  hi = block_reduce3<false>(hi, sh);
+  if (threadIdx.x < 3) meta[META_HEAD + 3 * blockIdx.x + threadIdx.x] = (int32_t)(uint32_t)hi.v[threadIdx.x];
+}
+
+// one workgroup: the global maxima over the B items, the depth (bit_length of the largest) and the flag
+__global__ __launch_bounds__(NT) void pcm_meta_kernel(int B, int32_t* __restrict__ meta) {
+  __shared__ long long sh[NW][3];
+  I3 hi{{0, 0, 0}};
+  for (int b = threadIdx.x; b < B; b += NT)
+    for (int a = 0; a < 3; ++a) {
+      const long long c = (long long)(uint32_t)meta[META_HEAD + 3 * b + a];
+      hi.v[a] = c > hi.v[a] ? c : hi.v[a];
+    }
+  hi = block_reduce3<false>(hi, sh);
+  if (threadIdx.x == 0) {
+    const bool bad = (hi.v[0] >> 31) & 1;
+    hi.v[0] &= 0x7fffffffll;
+    long long m = hi.v[0] > hi.v[1] ? hi.v[0] : hi.v[1];
+    m = m > hi.v[2] ? m : hi.v[2];
+    for (int a = 0; a < 3; ++a) meta[a] = (int32_t)hi.v[a];
+    meta[3] = m == 0 ? 0 : 64 - __clzll(m);
+    meta[4] = (bad || m > 65535) ? 1 : 0;
+    meta[5] = meta[6] = meta[7] = 0;
+  }
+}
+
+// PCM order ids: 0 z, 1 z-trans, 2 hilbert, 3 hilbert-trans (the library's curves at the meta block's depth, batch << 3 depth above), 4..9 the
+// axis orders xyz xzy yxz yzx zxy zyx in closed form: with c1 the first-named axis' cell and m1, m2, m3 the global maxima in the order's
+// sequence, s(m) = +1 for even m else -1 and e(m) = m + (m & 1):  code = b m1 m2 m3 + e(m3) m1 m2 + s(m3) (e(m2) m1 + s(m2) c1).
+__constant__ const int8_t AXES[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+
+__global__ __launch_bounds__(NT) void pcm_encode_kernel(int N, long long rows, int order, const int32_t* __restrict__ grid,
+                                                        const int32_t* __restrict__ meta, long long* __restrict__ code) {
+  const long long i = (long long)blockIdx.x * NT + threadIdx.x;
+  if (i >= rows) return;
+  const long long b = i / N;
+  if (order < 4) {
+    int depth = meta[3];
+    depth = depth > 16 ? 16 : depth;                      // flagged by the grid pass; the coordinates are masked
+    const uint32_t m = (1u << depth) - 1u;
+    const uint32_t c0 = (uint32_t)grid[i * 3 + 0] & m, c1 = (uint32_t)grid[i * 3 + 1] & m, c2 = (uint32_t)grid[i * 3 + 2] & m;
+    const u64 curve = depth == 0 ? 0ull : curve_code(order, c0, c1, c2, depth);   // depth 0: one cell, the code is the batch id
+    code[i] = (long long)(((u64)b << (3 * depth)) | curve);
+  } else {
+    const int8_t* ax = AXES[order - 4];
+    // in u64, where sums and products wrap as the reference's int64 tensors do (two's complement: -1 is ~0)
+    const u64 c1 = (u64)(long long)grid[i * 3 + ax[0]], m1 = (u64)(long long)meta[ax[0]], m2 = (u64)(long long)meta[ax[1]],
+              m3 = (u64)(long long)meta[ax[2]];
+    const u64 s2 = (m2 & 1) ? ~0ull : 1ull, s3 = (m3 & 1) ? ~0ull : 1ull, e2 = m2 + (m2 & 1), e3 = m3 + (m3 & 1);
+    code[i] = (long long)((u64)b * m1 * m2 * m3 + e3 * m1 * m2 + s3 * (e2 * m1 + s2 * c1));
+  }
+}
+
+// The whole signed sort of n <= SMALL_SORT keys in ONE workgroup: eight LSD passes over (key, index) in the scratch's two buffers, a
+// pass whose digit is the same in every key skipped (the decision is the workgroup's own: no host read, no pass count to bound).
+// k0/k1/v0/v1 are read and written in turn, hence not __restrict__; __syncthreads orders the workgroup's global stores and loads.
+__global__ __launch_bounds__(NT) void small_sort_kernel(int n, const u64* __restrict__ code, u64* k0, u64* k1, uint32_t* v0, uint32_t* v1,
+                                                        long long* __restrict__ order, long long* __restrict__ inverse) {
+  __shared__ RadixLds<NW> lds;
+  __shared__ uint32_t h[256];
+  const int tid = threadIdx.x;
+  const u64* kin = code;
+  const uint32_t* vin = nullptr;
+  int nxt = 0;
+  for (int p = 0; p < 8; ++p) {
+    const int shift = 8 * p;
+    const uint32_t flip = p == 7 ? 0x80u : 0u;
+    h[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += NT) atomicAdd(&h[digit_of(kin[i], shift, 0, flip)], 1u);
+    __syncthreads();
+    if (__syncthreads_or(h[tid] == (uint32_t)n)) continue;          // uniform: every thread sees the same answer
+    uint32_t all;
+    lds.digit_base[tid] = block_excl_scan<NW>(h[tid], lds.wt, all);
+    u64* kout = nxt ? k1 : k0;
+    uint32_t* vout = nxt ? v1 : v0;
+    u64 kn = 0; uint32_t vn = 0;
+    if (tid < n) { kn = kin[tid]; vn = vin ? vin[tid] : (uint32_t)tid; }
+    for (int base = 0; base < n; base += NT) {
+      radix_round_begin<NW>(lds);
+      const int i = base + tid;
+      const bool valid = i < n;
+      const u64 k = kn; const uint32_t v = vn;
+      if (i + NT < n) { kn = kin[i + NT]; vn = vin ? vin[i + NT] : (uint32_t)(i + NT); }   // the next round's, in flight over the barriers
+      const uint32_t dst = radix_round_dst<NW>(lds, valid, valid ? digit_of(k, shift, 0, flip) : 0u);
+      if (valid) { kout[dst] = k; vout[dst] = v; }
+      __syncthreads();
+    }
+    kin = kout; vin = vout; nxt ^= 1;
+  }
+  for (int i = tid; i < n; i += NT) {
+    const uint32_t v = vin ? vin[i] : (uint32_t)i;
+    order[i] = (long long)v;
+    inverse[v] = (long long)i;
+  }
+}
+
+// rows of up to 8 tensors moved by one index: dst_t[i] = src_t[index[i]].  V floats per load (4 where every row of the tensor is 16-byte
+// aligned); an index outside [0, rows) gives a row of zeros.
+struct GatherArgs {
+  const float* src[U3D_SER_GATHER_MAX];
+  float* dst[U3D_SER_GATHER_MAX];
+  int32_t channels[U3D_SER_GATHER_MAX];
+  int32_t vec[U3D_SER_GATHER_MAX];
+};
+
+template <typename VT>
+__device__ __forceinline__ void gather_tensor(long long rows, uint32_t per, const long long* __restrict__ index, const VT* __restrict__ src,
+                                              VT* __restrict__ dst) {
+  const unsigned long long total = (unsigned long long)rows * per, step = (unsigned long long)gridDim.x * NT;
+  for (unsigned long long e = (unsigned long long)blockIdx.x * NT + threadIdx.x; e < total; e += step) {
+    unsigned long long row; uint32_t col;
+    if (total < (1ull << 32)) { row = (uint32_t)e / per; col = (uint32_t)e - (uint32_t)row * per; }
+    else { row = e / per; col = (uint32_t)(e - row * per); }
+    const long long j = index[row];
+    VT x{};
+    if ((unsigned long long)j < (unsigned long long)rows) x = src[(unsigned long long)j * per + col];
+    dst[e] = x;
+  }
+}
+
+__global__ __launch_bounds__(NT) void gather_rows_kernel(long long rows, const long long* __restrict__ index, GatherArgs a) {
+  const int t = blockIdx.y;
+  if (a.vec[t]) gather_tensor<float4>(rows, (uint32_t)a.channels[t] / 4u, index, (const float4*)a.src[t], (float4*)a.dst[t]);
+  else gather_tensor<float>(rows, (uint32_t)a.channels[t], index, a.src[t], a.dst[t]);
+}
+
+bool bad_pcm(int B, int N) { return B < 1 || N < 1 || (long long)B * N > U3D_SER_MAX_ROWS; }
 
 }  // namespace
 
@@ -312,6 +504,62 @@ int u3d_ser_pool_emit(int K, int N, int M, int shift, int key_bits, const int64_
   Scratch p;
   carve(scratch, K, M, &p);
   radix_sort(p, K, M, key_bits, 0, (const u64*)pcode, true, (long long*)porder, (long long*)pinverse, st);
+  return launched();
+}
+
+int u3d_ser_pcm_grid(int B, int N, const float* pos, float grid_size, int32_t* grid, int32_t* meta, void* stream) {
+  if (bad_pcm(B, N) || !pos || !grid || !meta || !(grid_size > 0.f) || !(grid_size < 3.0e38f)) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  pcm_grid_kernel<<<B, NT, 0, st>>>(N, grid_size, pos, grid, meta);
+  pcm_meta_kernel<<<1, NT, 0, st>>>(B, meta);
+  return launched();
+}
+
+int u3d_ser_pcm_encode(int B, int N, int order, const int32_t* grid, const int32_t* meta, int64_t* code, void* stream) {
+  if (bad_pcm(B, N) || order < 0 || order >= U3D_SER_PCM_ORDERS || !grid || !meta || !code) return 1;
+  const long long rows = (long long)B * N;
+  pcm_encode_kernel<<<blocks(rows, NT), NT, 0, (hipStream_t)stream>>>(N, rows, order, grid, meta, (long long*)code);
+  return launched();
+}
+
+int u3d_ser_sort_signed(int N, const int64_t* code, int64_t* order, int64_t* inverse, void* scratch, void* stream) {
+  if (N < 1 || !code || !order || !inverse || !scratch) return 1;
+  if (N > U3D_SER_MAX_ROWS) return 2;
+  hipStream_t st = (hipStream_t)stream;
+  Scratch s;
+  carve(scratch, 1, N, &s);
+  if (N <= SMALL_SORT)
+    small_sort_kernel<<<1, NT, 0, st>>>(N, (const u64*)code, s.keys[0], s.keys[1], s.vals[0], s.vals[1], (long long*)order, (long long*)inverse);
+  else
+    radix_sort(s, 1, N, 64, 0, (const u64*)code, true, (long long*)order, (long long*)inverse, st, true);
+  return launched();
+}
+
+int u3d_ser_pcm_order(int B, int N, const float* pos, float grid_size, int order, int32_t* grid, int32_t* meta, int64_t* code,
+                      int64_t* order_out, int64_t* inverse, void* scratch, void* stream) {
+  if (order < 0 || order >= U3D_SER_PCM_ORDERS) return 1;
+  if (int rc = u3d_ser_pcm_grid(B, N, pos, grid_size, grid, meta, stream)) return rc;
+  if (int rc = u3d_ser_pcm_encode(B, N, order, grid, meta, code, stream)) return rc;
+  return u3d_ser_sort_signed(B * N, code, order_out, inverse, scratch, stream);
+}
+
+int u3d_ser_gather_rows(long long rows, int T, const int64_t* index, const void* const* src, void* const* dst, const int32_t* channels,
+                        void* stream) {
+  if (rows < 1 || T < 1 || T > U3D_SER_GATHER_MAX || !index || !src || !dst || !channels) return 1;
+  if (rows > U3D_SER_MAX_ROWS) return 2;
+  GatherArgs a{};
+  long long most = 0;
+  for (int t = 0; t < T; ++t) {
+    if (!src[t] || !dst[t] || src[t] == dst[t] || channels[t] < 1 || channels[t] > U3D_SER_GATHER_MAX_CHANNELS) return 1;
+    a.src[t] = (const float*)src[t];
+    a.dst[t] = (float*)dst[t];
+    a.channels[t] = channels[t];
+    a.vec[t] = channels[t] % 4 == 0 && aligned16(src[t]) && aligned16(dst[t]);
+    const long long work = rows * (channels[t] / (a.vec[t] ? 4 : 1));
+    most = work > most ? work : most;
+  }
+  const long long nb = (most + NT - 1) / NT;      // the kernel strides over what 4096 workgroups do not cover
+  gather_rows_kernel<<<dim3((unsigned)(nb < 4096 ? nb : 4096), T), NT, 0, (hipStream_t)stream>>>(rows, (const long long*)index, a);
   return launched();
 }
 

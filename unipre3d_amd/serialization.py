@@ -39,6 +39,12 @@ SIGNATURES = {   # include/unipre3d_serialization.h
     "u3d_ser_patch_padding": (_i, [_i, _i, _ll, _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
     "u3d_ser_pool_count": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "u3d_ser_pool_emit": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # PCM's order serialization (unipre3d_amd/pcm_order.py)
+    "u3d_ser_pcm_grid": (_i, [_i, _i, _vp, ctypes.c_float, _vp, _vp, _vp]),
+    "u3d_ser_pcm_encode": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    "u3d_ser_sort_signed": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_ser_pcm_order": (_i, [_i, _i, _vp, ctypes.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "u3d_ser_gather_rows": (_i, [_ll, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(SIGNATURES)
 
