@@ -35,6 +35,11 @@ __global__ void zbuf_min_kernel(int N, int H, int W, int total, float fx, float 
               ((unsigned long long)__float_as_uint(d == 0.f ? 0.f : d) << 32) | (unsigned)(t - b * N));
 }
 
+__global__ void zbuf_fill_kernel(size_t words, unsigned long long* __restrict__ zbuf) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < words) zbuf[t] = ~0ull;
+}
+
 __global__ void gather_kernel(int N, int C, int H, int W, int total, float fx, float fy, float cx, float cy,
                               const float* __restrict__ camera_points, const float* __restrict__ feat,
                               const unsigned long long* __restrict__ zbuf, float* __restrict__ mapped, int32_t* __restrict__ sel) {
@@ -132,7 +137,9 @@ int u3d_zbuffer_fusion_forward(int B, int N, int C, int H, int W, float fx, floa
   if (!camera_points || !image_features || !mapped || !sel || !zbuf) return 1;
   hipStream_t s = (hipStream_t)stream;
   const int total = B * N;
-  (void)hipMemsetAsync(zbuf, 0xFF, u3d_zbuffer_fusion_zbuf_bytes(B, H, W), s);   // 0xFF: no winner
+  // all-ones: no winner (a kernel: a captured memset node did not replay with its 0xFF value)
+  const size_t words = (size_t)B * H * W;
+  hipLaunchKernelGGL(zbuf_fill_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, words, (unsigned long long*)zbuf);
   hipLaunchKernelGGL(zbuf_min_kernel, dim3((total + 255) / 256), dim3(256), 0, s, N, H, W, total, fx, fy, cx, cy, camera_points,
                      (unsigned long long*)zbuf);
   hipLaunchKernelGGL(gather_kernel, dim3((total + 3) / 4), dim3(256), 0, s, N, C, H, W, total, fx, fy, cx, cy, camera_points,
