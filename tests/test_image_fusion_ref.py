@@ -181,6 +181,9 @@ def test_library_is_built_and_bound():
     assert lib.u3d_imgfus_stats_chunks(12, 5, 4, 4) == 0                  # Cin % G != 0
     for rows in (1, 64, 300, 4096, 10 ** 6):
         assert lib.u3d_imgfus_row_splits(rows) == IR.row_splits(rows)
+    tok = __import__("unipre3d_amd.tokenizer", fromlist=["load"]).load()   # one split rule (csrc/u3d_mfma_tile.h) behind both exports
+    for rows in (1, 255, 256, 257, 8192, 16384, 16385):
+        assert lib.u3d_imgfus_row_splits(rows) == tok.u3d_tok_wgrad_splits(rows) == IR.row_splits(rows)
     assert lib.u3d_imgfus_stats_scratch_bytes(32, 128, 32, 128, 128) == 32 * 32 * 8 * 16
     assert lib.u3d_imgfus_backward_scratch_bytes(2, 128, 128, 384) < 1 << 20
     assert lib.u3d_imgfus_backward_scratch_bytes(2, 128, 128, 8193) == 0

@@ -1,24 +1,24 @@
 // libunipre3d_image_fusion.so: GroupNorm + 1x1 convolution of the object-level image branch, evaluated only at the pixel columns the
 // z-buffer fusion selects (include/unipre3d_image_fusion.h).  One bandwidth pass over the decoder map for GroupNorm's statistics; the
-// forward is one f32-MFMA product whose operand prologue normalises the gathered rows; the backward is one split product
-// S = dout^T xhat (with s = column sums of dout on the side) and two small finishing kernels.  f64 sums in a fixed order, no atomics.
+// forward is the shared f32-MFMA product (u3d_mfma_tile.h) with an operand prologue that normalises the gathered rows; the backward is
+// the shared split weight-gradient product S = dout^T xhat (with s = column sums of dout on the side) and two small finishing kernels.
+// f64 sums in a fixed order, no atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "unipre3d_image_fusion.h"
+#include "u3d_mfma_tile.h"
 #include "u3d_util.h"
 
 namespace {
 
 using namespace u3d_util;
+using namespace u3d_mfma_tile;                // NT, the block tile, gemm(), wgrad_kernel and its split rule
 
-constexpr int NT = 256;
-constexpr int BM = 64, BN = 64, BK = 32;      // product block tile: 64 x 64, 32 of the reduction per LDS stage
 constexpr int CHUNK = 8192;                   // floats of a group one workgroup of the statistics pass sums (a multiple of 4)
 constexpr int MAX_CHANNELS = 8192;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- statistics -------------------------------------------------------------------------------------------------------------------
 int stats_chunks(long long L) { return (int)((L + CHUNK - 1) / CHUNK); }
@@ -121,121 +121,27 @@ struct ADout {     // the cotangent of a winner row, zeros of any other (whateve
 
 uint32_t group_magic(int cpg) { return cpg == 1 ? 0u : (uint32_t)((1ull << 32) / (uint32_t)cpg + 1); }
 
-// ---- forward: out = [winner] (y W^T + bias) on v_mfma_f32_16x16x4_f32, each wave a 32 x 32 quarter of the tile as 2 x 2 MFMA blocks ----
-__global__ __launch_bounds__(NT) void rows_forward_kernel(long long R, int K, int Nc, ANorm aop, const float* __restrict__ W,
-                                                          const float* __restrict__ bias, float* __restrict__ out) {
-  __shared__ float As[BM][BK + 1];
-  __shared__ float Bs[BK][BN + 4];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const long long r0 = (long long)blockIdx.x * BM;
-  const int n0 = blockIdx.y * BN;
-  const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-  f32x4 acc[2][2];
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int ar = tid >> 2, ac = (tid & 3) * 8;     // 4 threads per row (and per column of W), 8 consecutive k each
-  const bool alive = r0 + ar < R;
-  const ANorm::Ctx ctx = aop.prep(alive ? r0 + ar : 0);
-  const int nn = n0 + ar;
-  for (int c0 = 0; c0 < K; c0 += BK) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = c0 + ac + j;
-      As[ar][ac + j] = (alive && c < K) ? aop.get(ctx, c) : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = c0 + ac + j;
-      Bs[ac + j][ar] = (nn < Nc && c < K) ? W[(size_t)nn * K + c] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 4) {
-      float a[2], b[2];
-      for (int i = 0; i < 2; ++i) a[i] = As[wr + i * 16 + (lane & 15)][kk + (lane >> 4)];
-      for (int j = 0; j < 2; ++j) b[j] = Bs[kk + (lane >> 4)][wc + j * 16 + (lane & 15)];
-      for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
+// ---- what the shared products (u3d_mfma_tile.h) store ------------------------------------------------------------------------------
+struct EWinner {   // forward: out = [winner] (y W^T + bias)
+  const int32_t* sel;
+  const float* bias;
+  float* out;
+  int Nc;
+  __device__ __forceinline__ void store(long long r, int col, float v) const { out[r * Nc + col] = sel[r] >= 0 ? v + bias[col] : 0.f; }
+};
+struct ColSum {    // backward: the workgroups of the first column tile also add spart[split][o] = sum of dout(r, o), row after row
+  float* spart;
+  struct Acc { float sum = 0.f; };
+  __device__ __forceinline__ void stage(Acc& a, const ATile& As, int co0, int tid) const {
+    if (co0 == 0 && tid < BM)
+      for (int q = 0; q < BK; ++q) a.sum += As[tid][q];
   }
-  for (int i = 0; i < 2; ++i)
-    for (int v = 0; v < 4; ++v) {
-      const long long r = r0 + wr + i * 16 + (lane >> 4) * 4 + v;
-      if (r >= R) continue;
-      const bool win = aop.v.sel[r] >= 0;
-      for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wc + j * 16 + (lane & 15);
-        if (col < Nc) out[r * Nc + col] = win ? acc[i][j][v] + bias[col] : 0.f;
-      }
-    }
-}
+  __device__ __forceinline__ void finish(const Acc& a, int split, int ci0, int co0, int Ma, int tid) const {
+    if (co0 == 0 && tid < BM && ci0 + tid < Ma) spart[(size_t)split * Ma + ci0 + tid] = a.sum;
+  }
+};
 
 // ---- backward ---------------------------------------------------------------------------------------------------------------------
-long long rows_per_split(long long rows) {
-  const long long s = std::max(1ll, std::min(64ll, (rows + 255) / 256));
-  return ((rows + s - 1) / s + BK - 1) / BK * BK;
-}
-int row_splits(long long rows) { const long long rps = rows_per_split(rows); return (int)((rows + rps - 1) / rps); }
-
-// part[split] (Cout x Cin) = sum over the split's rows of dout(r, o) xhat(r, c), rows in ascending 32-row steps; the workgroups of the
-// first column tile also add spart[split][o] = sum of dout(r, o), row after row
-__global__ __launch_bounds__(NT) void split_product_kernel(long long R, int Ma, int Ng, ADout aop, AXhat gop, long long rps,
-                                                           float* __restrict__ part, float* __restrict__ spart) {
-  __shared__ float As[BM][BK + 1];    // As[o][row]
-  __shared__ float Gs[BK][BN + 4];    // Gs[row][c]
-  const int tci = blocks(Ma, BM);
-  const int ci0 = (blockIdx.x % tci) * BM, co0 = (blockIdx.x / tci) * BN;
-  const int split = blockIdx.y;
-  const long long r_beg = split * rps, r_end = min(R, r_beg + rps);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-  f32x4 acc[2][2];
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float colsum = 0.f;
-  const int lr = tid >> 3, lc = (tid & 7) * 8;    // 8 threads per row, 8 consecutive channels each
-  for (long long r0 = r_beg; r0 < r_end; r0 += BK) {
-    const long long r = r0 + lr;
-    const bool live = r < r_end;
-    const ADout::Ctx ca = aop.prep(live ? r : 0);
-    const AXhat::Ctx cg = gop.prep(live ? r : 0);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = ci0 + lc + j;
-      As[lc + j][lr] = (live && c < Ma) ? aop.get(ca, c) : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = co0 + lc + j;
-      Gs[lr][lc + j] = (live && c < Ng) ? gop.get(cg, c) : 0.f;
-    }
-    __syncthreads();
-    if (co0 == 0 && tid < BM)
-      for (int q = 0; q < BK; ++q) colsum += As[tid][q];
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 4) {
-      float a[2], b[2];
-      for (int i = 0; i < 2; ++i) a[i] = As[wr + i * 16 + (lane & 15)][kk + (lane >> 4)];
-      for (int j = 0; j < 2; ++j) b[j] = Gs[kk + (lane >> 4)][wc + j * 16 + (lane & 15)];
-      for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  float* p = part + (size_t)split * Ma * Ng;
-  for (int i = 0; i < 2; ++i)
-    for (int v = 0; v < 4; ++v) {
-      const int ci = ci0 + wr + i * 16 + (lane >> 4) * 4 + v;
-      if (ci >= Ma) continue;
-      for (int j = 0; j < 2; ++j) {
-        const int co = co0 + wc + j * 16 + (lane & 15);
-        if (co < Ng) p[(size_t)ci * Ng + co] = acc[i][j][v];
-      }
-    }
-  if (co0 == 0 && tid < BM && ci0 + tid < Ma) spart[(size_t)split * Ma + ci0 + tid] = colsum;
-}
-
 // S and s from the splits in order; dW = gamma S + beta s, dbias = s
 __global__ __launch_bounds__(NT) void finish_weight_kernel(int Cout, int Cin, int splits, const float* __restrict__ part,
                                                            const float* __restrict__ spart, const float* __restrict__ gamma,
@@ -298,7 +204,7 @@ struct BwdScratch {   // byte offsets, every one a multiple of 16
   size_t part, spart, S, s, total;
 };
 BwdScratch carve(long long R, int Cin, int Cout) {
-  const size_t splits = (size_t)row_splits(R);
+  const size_t splits = (size_t)wgrad_splits(R);
   auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
   BwdScratch b;
   b.part = 0;
@@ -319,7 +225,7 @@ int u3d_imgfus_stats_chunks(int Cin, int G, int H, int W) {
   return check_map(1, Cin, G, H, W) ? 0 : stats_chunks((long long)(Cin / G) * H * W);
 }
 
-int u3d_imgfus_row_splits(long long rows) { return rows < 1 ? 0 : row_splits(rows); }
+int u3d_imgfus_row_splits(long long rows) { return rows < 1 ? 0 : wgrad_splits(rows); }
 
 size_t u3d_imgfus_stats_scratch_bytes(int B, int Cin, int G, int H, int W) {
   if (check_map(B, Cin, G, H, W)) return 0;
@@ -351,7 +257,7 @@ int u3d_imgfus_rows_forward(const float* rows, const int32_t* sel, const float* 
   hipStream_t st = (hipStream_t)stream;
   const long long R = (long long)B * N;
   const ANorm aop{RowView{rows, sel, stats, N, Cin, G, group_magic(Cin / G)}, gamma, beta};
-  rows_forward_kernel<<<dim3(blocks(R, BM), blocks(Cout, BN)), NT, 0, st>>>(R, Cin, Cout, aop, weight, bias, out);
+  gemm<ANorm, true, EWinner>(R, Cin, Cout, aop, weight, Cin, 0, EWinner{sel, bias, out, Cout}, st);
   return launched();
 }
 
@@ -369,10 +275,10 @@ int u3d_imgfus_rows_backward(const float* dout, const float* rows, const int32_t
   float* spart = (float*)((char*)scratch + sc.spart);
   float* S = (float*)((char*)scratch + sc.S);
   float* s = (float*)((char*)scratch + sc.s);
-  const int splits = row_splits(R);
+  const int splits = wgrad_splits(R);
   const RowView rv{rows, sel, stats, N, Cin, G, group_magic(Cin / G)};
-  split_product_kernel<<<dim3(blocks(Cout, BM) * blocks(Cin, BN), splits), NT, 0, st>>>(R, Cout, Cin, ADout{dout, sel, Cout}, AXhat{rv},
-                                                                                      rows_per_split(R), part, spart);
+  wgrad_kernel<ADout, AXhat, ColSum><<<dim3(blocks(Cout, BM) * blocks(Cin, BN), splits), NT, 0, st>>>(
+      R, Cout, Cin, ADout{dout, sel, Cout}, AXhat{rv}, wgrad_rows_per_split(R), part, ColSum{spart});
   finish_weight_kernel<<<blocks((long long)Cout * Cin, NT), NT, 0, st>>>(Cout, Cin, splits, part, spart, gamma, beta, S, s, dweight, dbias);
   finish_affine_kernel<<<blocks(Cin, 64), NT, 0, st>>>(Cout, Cin, weight, S, s, dgamma, dbeta);
   return launched();

@@ -8,22 +8,27 @@
 
 #include "unipre3d_sparseconv.h"
 #include "u3d_keysort.h"
+#include "u3d_mfma_tile.h"
 
 namespace {
 
 using namespace u3d_util;
 
+// the MFMA tile pieces: constants, LDS tile types, the wave's quarter and the accumulator-to-position map are shared; the loops around
+// them are this library's own, and so is the fragment-load-and-MFMA block of its two kernels, a copy of tile::stage_product to be
+// kept in step with it: called as the function, the block compiled to other code here (wgrad_mfma_kernel 45 -> 32 VGPRs and 16 -> 32
+// AGPRs, gemm_mfma_kernel 42 -> 47 VGPRs) and the weight gradient measured 4 - 9 % slower at 32 - 128 channels (EXPERIMENTS.md)
+namespace tile = u3d_mfma_tile;
 constexpr int NT = 256;              // threads per workgroup (four waves)
 constexpr int NW = NT / 64;
 constexpr int ITEMS = 16;            // rounds of NT elements per tile of the sort and scan passes
 constexpr int TILE = NT * ITEMS;
 constexpr int SCAN_NT = 1024;        // the one-workgroup exclusive scan
 // the class boundaries are public (unipre3d_sparseconv.h): the tests place their shapes on both sides of each
-constexpr int BM = U3D_SPCONV_TILE, BN = U3D_SPCONV_TILE, BK = U3D_SPCONV_KSTEP;   // GEMM block tile: 64 rows x 64 columns, 32 of the reduction per LDS stage
+using tile::BM; using tile::BN; using tile::BK;   // GEMM block tile: 64 rows x 64 columns, 32 of the reduction per LDS stage
+static_assert(BM == U3D_SPCONV_TILE && BN == U3D_SPCONV_TILE && BK == U3D_SPCONV_KSTEP && NT == tile::NT, "the public class boundaries are the shared tile");
 constexpr int SMALL_C = U3D_SPCONV_SMALL_C;   // a channel count at or below this takes the VALU kernels (the stem's Cin = 3 / 6)
 constexpr int WAVE_SUM_SPLITS = U3D_SPCONV_WAVE_SUM_SPLITS;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 inline int bit_len(unsigned long long v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
 
@@ -236,16 +241,15 @@ __global__ __launch_bounds__(NT) void gemm_mfma_kernel(int R, int K, int Cin, in
                                                        const int32_t* __restrict__ list_row, const float* __restrict__ A,
                                                        const float* __restrict__ W, const float* __restrict__ bias,
                                                        const int32_t* __restrict__ mask, float* __restrict__ Y) {
-  __shared__ float As[BM][BK + 1];
-  __shared__ float Bs[BK][BN + 4];
+  __shared__ tile::ATile As;
+  __shared__ tile::BTile Bs;
   __shared__ int srcs[BM];
   const bool list = list_row != nullptr;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int e0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-  f32x4 acc[2][2];
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const tile::Wave w = tile::wave_of(tid);
+  tile::f32x4 acc[2][2];
+  tile::zero(acc);
   const int ar = tid >> 2, ac = (tid & 3) * 8;     // A stage: 4 threads per row, 8 consecutive channels each
   const int bk = tid >> 3, bc = (tid & 7) * 8;     // B stage: 8 threads per reduction row, 8 consecutive columns each
   for (int k = 0; k < K; ++k) {
@@ -269,10 +273,10 @@ __global__ __launch_bounds__(NT) void gemm_mfma_kernel(int R, int K, int Cin, in
       }
       __syncthreads();
 #pragma unroll
-      for (int kk = 0; kk < BK; kk += 4) {
+      for (int kk = 0; kk < BK; kk += 4) {         // tile::stage_product's block (the note at `namespace tile`)
         float a[2], b[2];
-        for (int i = 0; i < 2; ++i) a[i] = As[wr + i * 16 + (lane & 15)][kk + (lane >> 4)];
-        for (int j = 0; j < 2; ++j) b[j] = Bs[kk + (lane >> 4)][wc + j * 16 + (lane & 15)];
+        for (int i = 0; i < 2; ++i) a[i] = As[w.wr + i * 16 + (w.lane & 15)][kk + (w.lane >> 4)];
+        for (int j = 0; j < 2; ++j) b[j] = Bs[kk + (w.lane >> 4)][w.wc + j * 16 + (w.lane & 15)];
         for (int i = 0; i < 2; ++i)
           for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
       }
@@ -281,12 +285,12 @@ __global__ __launch_bounds__(NT) void gemm_mfma_kernel(int R, int K, int Cin, in
   }
   for (int i = 0; i < 2; ++i)
     for (int v = 0; v < 4; ++v) {
-      const int e = e0 + wr + i * 16 + (lane >> 4) * 4 + v;
+      const int e = tile::acc_row(w, e0, i, v);
       if (e >= R) continue;
       const int o = list ? list_row[e] : e;
       const bool zero = mask && mask[o] != o;
       for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wc + j * 16 + (lane & 15);
+        const int col = tile::acc_col(w, n0, j);
         if (col < Cout) Y[(size_t)o * Cout + col] = zero ? 0.f : acc[i][j][v] + (bias ? bias[col] : 0.f);
       }
     }
@@ -338,18 +342,17 @@ int wgrad_rows_per_split(int R, int splits) { return blocks(blocks(R, splits), B
 __global__ __launch_bounds__(NT) void wgrad_mfma_kernel(int R, int K, int Cin, int Cout, const int32_t* __restrict__ tab, int gather_g,
                                                         const float* __restrict__ A, const float* __restrict__ G, int rps,
                                                         float* __restrict__ part) {
-  __shared__ float As[BM][BK + 1];    // As[ci][row]
-  __shared__ float Gs[BK][BN + 4];    // Gs[row][co]
+  __shared__ tile::ATile As;    // As[ci][row]
+  __shared__ tile::BTile Gs;    // Gs[row][co]
   __shared__ int srcs[BK];
   const int tci = blocks(Cin, BM);
   const int ci0 = (blockIdx.x % tci) * BM, co0 = (blockIdx.x / tci) * BN;
   const int k = blockIdx.y, split = blockIdx.z;
   const int r_beg = split * rps, r_end = min(R, r_beg + rps);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-  f32x4 acc[2][2];
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int tid = threadIdx.x;
+  const tile::Wave w = tile::wave_of(tid);
+  tile::f32x4 acc[2][2];
+  tile::zero(acc);
   const int lr = tid >> 3, lc = (tid & 7) * 8;    // 8 threads per row, 8 consecutive channels each
   for (int r0 = r_beg; r0 < r_end; r0 += BK) {
     int s = -1;
@@ -371,10 +374,10 @@ __global__ __launch_bounds__(NT) void wgrad_mfma_kernel(int R, int K, int Cin, i
     }
     __syncthreads();
 #pragma unroll
-    for (int kk = 0; kk < BK; kk += 4) {
+    for (int kk = 0; kk < BK; kk += 4) {           // tile::stage_product's block (the note at `namespace tile`)
       float a[2], b[2];
-      for (int i = 0; i < 2; ++i) a[i] = As[wr + i * 16 + (lane & 15)][kk + (lane >> 4)];
-      for (int j = 0; j < 2; ++j) b[j] = Gs[kk + (lane >> 4)][wc + j * 16 + (lane & 15)];
+      for (int i = 0; i < 2; ++i) a[i] = As[w.wr + i * 16 + (w.lane & 15)][kk + (w.lane >> 4)];
+      for (int j = 0; j < 2; ++j) b[j] = Gs[kk + (w.lane >> 4)][w.wc + j * 16 + (w.lane & 15)];
       for (int i = 0; i < 2; ++i)
         for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
     }
@@ -383,10 +386,10 @@ __global__ __launch_bounds__(NT) void wgrad_mfma_kernel(int R, int K, int Cin, i
   float* p = part + ((size_t)split * K + k) * Cin * Cout;
   for (int i = 0; i < 2; ++i)
     for (int v = 0; v < 4; ++v) {
-      const int ci = ci0 + wr + i * 16 + (lane >> 4) * 4 + v;
+      const int ci = tile::acc_row(w, ci0, i, v);
       if (ci >= Cin) continue;
       for (int j = 0; j < 2; ++j) {
-        const int co = co0 + wc + j * 16 + (lane & 15);
+        const int co = tile::acc_col(w, co0, j);
         if (co < Cout) p[(size_t)ci * Cout + co] = acc[i][j][v];
       }
     }

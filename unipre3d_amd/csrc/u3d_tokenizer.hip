@@ -1,7 +1,7 @@
 // libunipre3d_tokenizer.so: the group tokenizer (mini-PointNet `Encoder`) of the transformer and Mamba3D backbones, forward and backward
 // in fp32 (include/unipre3d_tokenizer.h).  BN1's statistics come from nine moments of the coordinates, the cat is replaced by a per-group
-// bias, and the backward is three phases separated by BatchNorm's two global sums.  One MFMA GEMM and one split weight-gradient
-// kernel serve every plain product: what differs between the products is how an operand element is made (a row of f2, relu(A x + d)
+// bias, and the backward is three phases separated by BatchNorm's two global sums.  The shared MFMA GEMM and split weight-gradient
+// kernel (u3d_mfma_tile.h) serve every plain product: what differs between the products is how an operand element is made (a row of f2, relu(A x + d)
 // from three coordinates, relu(s2 y3 + t2), dy3 from dh3m and y3) and what the epilogue adds, both template arguments.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,19 +9,18 @@
 #include <algorithm>
 
 #include "unipre3d_tokenizer.h"
+#include "u3d_mfma_tile.h"
 #include "u3d_util.h"
 
 namespace {
 
 using namespace u3d_util;
+using namespace u3d_mfma_tile;                // NT, the block tile, gemm(), wgrad_kernel and its split rule
 
-constexpr int NT = 256;
-constexpr int BM = 64, BN = 64, BK = 32;      // GEMM block tile: 64 rows x 64 columns, 32 of the reduction per LDS stage
 constexpr int C1 = 128, C2 = 256, C3 = 512;   // the reference's widths
 constexpr int F1_A = 0, F1_D = 384, F1_AH = 512, F1_DH = 896, F1_MEAN = 1024, F1_INV = 1152;   // fold1
 constexpr int F2_S = 0, F2_T = 512, F2_MEAN = 1024, F2_INV = 1536;                              // fold2
 constexpr int SLAB = 32, PHASES = 8;          // dh3m: columns per workgroup, row phases (NT = SLAB * PHASES)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- the input through its strides ---------------------------------------------------------------------------------------------
 struct XView {
@@ -119,134 +118,11 @@ struct EMaskH1 {      // dh1m = [h1 > 0] (df2 W2)
   }
 };
 
-// Y = op(A) B on v_mfma_f32_16x16x4_f32; BT: B[k][n] = W[n ldw + woff + k] (Y = A W^T), else B[k][n] = W[k ldw + woff + n] (Y = A W).
-// Each wave a 32 x 32 quarter of the 64 x 64 tile as 2 x 2 MFMA blocks.
-template <class AOp, bool BT, class Epi>
-__global__ __launch_bounds__(NT) void gemm_kernel(long long R, int K, int N, AOp aop, const float* __restrict__ W, int ldw, int woff,
-                                                  Epi epi) {
-  __shared__ float As[BM][BK + 1];
-  __shared__ float Bs[BK][BN + 4];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const long long r0 = (long long)blockIdx.x * BM;
-  const int n0 = blockIdx.y * BN;
-  const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-  f32x4 acc[2][2];
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int ar = tid >> 2, ac = (tid & 3) * 8;     // A stage: 4 threads per row, 8 consecutive k each
-  const bool alive = r0 + ar < R;
-  const typename AOp::Ctx ctx = aop.prep(alive ? r0 + ar : 0);
-  for (int c0 = 0; c0 < K; c0 += BK) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = c0 + ac + j;
-      As[ar][ac + j] = (alive && c < K) ? aop.get(ctx, c) : 0.f;
-    }
-    if (BT) {                                      // 4 threads per column, 8 consecutive k each
-      const int bn = tid >> 2, bk0 = (tid & 3) * 8, nn = n0 + bn;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int c = c0 + bk0 + j;
-        Bs[bk0 + j][bn] = (nn < N && c < K) ? W[(size_t)nn * ldw + woff + c] : 0.f;
-      }
-    } else {                                       // 8 threads per k, 8 consecutive columns each
-      const int bk = tid >> 3, bc = (tid & 7) * 8, c = c0 + bk;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int nn = n0 + bc + j;
-        Bs[bk][bc + j] = (c < K && nn < N) ? W[(size_t)c * ldw + woff + nn] : 0.f;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 4) {
-      float a[2], b[2];
-      for (int i = 0; i < 2; ++i) a[i] = As[wr + i * 16 + (lane & 15)][kk + (lane >> 4)];
-      for (int j = 0; j < 2; ++j) b[j] = Bs[kk + (lane >> 4)][wc + j * 16 + (lane & 15)];
-      for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  for (int i = 0; i < 2; ++i)
-    for (int v = 0; v < 4; ++v) {
-      const long long r = r0 + wr + i * 16 + (lane >> 4) * 4 + v;
-      if (r >= R) continue;
-      for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wc + j * 16 + (lane & 15);
-        if (col < N) epi.store(r, col, acc[i][j][v]);
-      }
-    }
-}
-
-template <class AOp, bool BT, class Epi>
-void gemm(long long R, int K, int N, const AOp& aop, const float* W, int ldw, int woff, const Epi& epi, hipStream_t st) {
-  gemm_kernel<AOp, BT, Epi><<<dim3(blocks(R, BM), blocks(N, BN)), NT, 0, st>>>(R, K, N, aop, W, ldw, woff, epi);
-}
-
 // ---- weight gradients: fixed-order split reductions ------------------------------------------------------------------------------
-long long wgrad_rows_per_split(long long rows) {
-  const long long s = std::max(1ll, std::min(64ll, (rows + 255) / 256));
-  return ((rows + s - 1) / s + BK - 1) / BK * BK;
-}
-int wgrad_splits(long long rows) { const long long rps = wgrad_rows_per_split(rows); return (int)((rows + rps - 1) / rps); }
 long long group_rows_per_split(long long M) { const long long s = std::max(1ll, std::min(32ll, (M + 63) / 64)); return (M + s - 1) / s; }
 int group_splits(long long M) { const long long gps = group_rows_per_split(M); return (int)((M + gps - 1) / gps); }
 long long stat_rows_per_split(long long R) { const long long s = std::max(1ll, std::min(256ll, (R + 511) / 512)); return (R + s - 1) / s; }
 int stat_splits(long long R) { const long long rps = stat_rows_per_split(R); return (int)((R + rps - 1) / rps); }
-
-// part[split] (Ma x Ng) = sum over the split's rows r of a(r, i) g(r, j), rows in ascending 32-row steps
-template <class AOp, class GOp>
-__global__ __launch_bounds__(NT) void wgrad_kernel(long long R, int Ma, int Ng, AOp aop, GOp gop, long long rps, float* __restrict__ part) {
-  __shared__ float As[BM][BK + 1];    // As[i][row]
-  __shared__ float Gs[BK][BN + 4];    // Gs[row][j]
-  const int tci = blocks(Ma, BM);
-  const int ci0 = (blockIdx.x % tci) * BM, co0 = (blockIdx.x / tci) * BN;
-  const int split = blockIdx.y;
-  const long long r_beg = split * rps, r_end = min(R, r_beg + rps);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-  f32x4 acc[2][2];
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int lr = tid >> 3, lc = (tid & 7) * 8;    // 8 threads per row, 8 consecutive channels each
-  for (long long r0 = r_beg; r0 < r_end; r0 += BK) {
-    const long long r = r0 + lr;
-    const bool live = r < r_end;
-    const typename AOp::Ctx ca = aop.prep(live ? r : 0);
-    const typename GOp::Ctx cg = gop.prep(live ? r : 0);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = ci0 + lc + j;
-      As[lc + j][lr] = (live && c < Ma) ? aop.get(ca, c) : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = co0 + lc + j;
-      Gs[lr][lc + j] = (live && c < Ng) ? gop.get(cg, c) : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 4) {
-      float a[2], b[2];
-      for (int i = 0; i < 2; ++i) a[i] = As[wr + i * 16 + (lane & 15)][kk + (lane >> 4)];
-      for (int j = 0; j < 2; ++j) b[j] = Gs[kk + (lane >> 4)][wc + j * 16 + (lane & 15)];
-      for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  float* p = part + (size_t)split * Ma * Ng;
-  for (int i = 0; i < 2; ++i)
-    for (int v = 0; v < 4; ++v) {
-      const int ci = ci0 + wr + i * 16 + (lane >> 4) * 4 + v;
-      if (ci >= Ma) continue;
-      for (int j = 0; j < 2; ++j) {
-        const int co = co0 + wc + j * 16 + (lane & 15);
-        if (co < Ng) p[(size_t)ci * Ng + co] = acc[i][j][v];
-      }
-    }
-}
 
 // out[i ldo + off + j] = sum over splits, in order, of part[split][i Ng + j]
 __global__ __launch_bounds__(NT) void split_sum_kernel(int Ma, int Ng, int splits, const float* __restrict__ part, float* __restrict__ out,
