@@ -172,7 +172,7 @@ U3DSource split_sh_source(const u3d_raster_desc& d, const float* means3D, const 
 // head_source for a forward.  The object-level head (mode 1) needs the across-point quaternion norms: preprocess_fwd computes them
 // itself when one workgroup holds the whole set (P <= 256), else they are launched here; both clear `qdot_zero` (may be null).
 U3DSource head_source_forward(const u3d_raster_desc& d, const u3d_head_desc& h, const float* head_out, const float* center,
-                              const U3DFused& f, float* qdot_zero, hipStream_t s) {
+                              const U3DFused& f, double* qdot_zero, hipStream_t s) {
   U3DSource src = head_source(d, h, head_out, center, f.qnorm);
   if (h.mode == 1) {
     if (u3d_preprocess_sorts(d)) { src.qnorm_out = f.qnorm; src.qdot_zero = qdot_zero; }
@@ -182,7 +182,7 @@ U3DSource head_source_forward(const u3d_raster_desc& d, const u3d_head_desc& h, 
 }
 
 // d(head_out) as the gradient sink: the channels of head_source; qdot collects the across-point quaternion term
-U3DGradSink head_sink(float* d_head_out, float* qdot) {
+U3DGradSink head_sink(float* d_head_out, double* qdot) {
   U3DGradSink sink{};
   sink.means = d_head_out; sink.opac = d_head_out + 3; sink.scales = d_head_out + 4; sink.rots = d_head_out + 7;
   sink.shs = d_head_out + 11; sink.qdot = qdot;
@@ -440,7 +440,7 @@ int u3d_render_loss_backward(const u3d_raster_desc* desc, const u3d_head_desc* h
   u3d_carve_fused(d, fused, &f);
   const BackwardScratch w = split_backward_scratch(backward_scratch, Lay);
   (void)hipMemsetAsync(w.acc, 0, Lay.acc_bytes, s);
-  (void)hipMemsetAsync(f.qdot, 0, sizeof(float) * 4 * d.n_items, s);
+  (void)hipMemsetAsync(f.qdot, 0, sizeof(double) * 4 * d.n_items, s);
   const U3DLoss L = make_loss(d, *loss, gt, f.partial, dloss);
   {
     ProfScope ps(3, s);

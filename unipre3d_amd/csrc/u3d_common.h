@@ -135,7 +135,7 @@ struct U3DSource {
   // act == 1 and P <= 256 (one workgroup holds the whole set): preprocess_fwd computes the norms itself, publishes them
   // here for the backward, and clears qdot_zero -- no separate quat_norms launch
   float* qnorm_out;
-  float* qdot_zero;
+  double* qdot_zero;
 };
 
 // Where per-Gaussian gradients go (same strides as the source; act != 0 chains through the activations).
@@ -143,7 +143,9 @@ struct U3DGradSink {
   float* means; float* shs; float* colors; float* opac; float* scales; float* rots; float* cov;
   float* shs_rest;      // split SH: gradient of coefficients 1.. (same layout as U3DSource::shs_rest), else null
   float* means2D;       // [NV][P][3] or null
-  float* qdot;          // [B][4] sum_i raw_rot[i][c] * g[i][c]  (act == 1; finished by u3d_quat_fixup)
+  double* qdot;         // [B][4] sum_i raw_rot[i][c] * g[i][c]  (act == 1; finished by u3d_quat_fixup).  f64: the blocks of a set meet in an atomic, and a
+                        // sum of fp32-valued terms in f64 is exact unless the blocks' terms differ by more than ~2^24 in magnitude (29 bits of
+                        // headroom less log2 of the block count), so the order in which three or more blocks arrive does not show (in fp32 it did)
 };
 
 // Optional fused render loss: utils/loss_utils.py:17-45 evaluated in the render epilogue /
@@ -161,20 +163,21 @@ struct U3DLayout {
   size_t geom_bytes, binning_bytes, image_bytes, backward_bytes, acc_bytes, num_rendered_offset, fused_bytes;
 };
 
-// fused scratch: [qnorm n_items*4][qdot n_items*4][loss partial NV*T]
+// fused scratch: [qnorm n_items*4 f32][qdot n_items*4 f64][loss partial NV*T]
 struct U3DFused {
-  float* qnorm; float* qdot; float* partial;
+  float* qnorm; double* qdot; float* partial;
 };
 static inline size_t u3d_carve_fused(const u3d_raster_desc& d, void* base, U3DFused* f) {
   const size_t NV = (size_t)d.n_items * d.views_per_item;
   const size_t T = u3d_tile_count(d);
   const size_t a = (((size_t)d.n_items * 4 * sizeof(float)) + 255) & ~(size_t)255;
+  const size_t a2 = (((size_t)d.n_items * 4 * sizeof(double)) + 255) & ~(size_t)255;
   if (f) {
     f->qnorm = (float*)base;
-    f->qdot = (float*)((char*)base + a);
-    f->partial = (float*)((char*)base + 2 * a);
+    f->qdot = (double*)((char*)base + a);
+    f->partial = (float*)((char*)base + a + a2);
   }
-  return 2 * a + (((NV * T * sizeof(float)) + 255) & ~(size_t)255) + 256;
+  return a + a2 + (((NV * T * sizeof(float)) + 255) & ~(size_t)255) + 256;
 }
 
 // partial-row buffer: U3D_PART_BLOCKS blocks of 64 sorted positions x 10 floats per tile (positions beyond go through f64
@@ -267,8 +270,8 @@ static inline bool u3d_sparse_bwd(const u3d_raster_desc& d, int head_mode) {
 }
 // true when preprocess_fwd also produces the per-view depth order (P <= 256): skip u3d_launch_depth_sort then
 bool u3d_preprocess_sorts(const u3d_raster_desc& d);
-void u3d_launch_quat_norms(const u3d_raster_desc& d, const float* rots, int s_rots, float* qnorm, float* qdot_zero, hipStream_t s);
-void u3d_launch_quat_fixup(const u3d_raster_desc& d, const float* rots, int s_rots, const float* qnorm, const float* qdot,
+void u3d_launch_quat_norms(const u3d_raster_desc& d, const float* rots, int s_rots, float* qnorm, double* qdot_zero, hipStream_t s);
+void u3d_launch_quat_fixup(const u3d_raster_desc& d, const float* rots, int s_rots, const float* qnorm, const double* qdot,
                            float* d_rots, hipStream_t s);
 void u3d_launch_depth_sort(const u3d_raster_desc& d, const U3DBuffers& b, const int32_t* radii, hipStream_t s);
 void u3d_launch_render_fwd(const u3d_raster_desc& d, const U3DBuffers& b, const float* bg, float* out_color,

@@ -191,7 +191,7 @@ __global__ __launch_bounds__(U3D_BLOCK) void preprocess_fwd_kernel(
         s_qn[threadIdx.x] = n;
         if (blockIdx.z == 0) {
           src.qnorm_out[item * 4 + threadIdx.x] = n;
-          if (src.qdot_zero) src.qdot_zero[item * 4 + threadIdx.x] = 0.f;
+          if (src.qdot_zero) src.qdot_zero[item * 4 + threadIdx.x] = 0.0;
         }
       }
       __syncthreads();
@@ -754,7 +754,7 @@ __global__ __launch_bounds__(U3D_BLOCK) void preprocess_bwd_kernel(
   }
   }
   if (src.act == 1) {
-    // block reduction of sum_i raw_q[i][c] * g[i][c]; one atomic per block and component
+    // block reduction of sum_i raw_q[i][c] * g[i][c]; one f64 atomic per block and component (U3DGradSink::qdot)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -764,7 +764,7 @@ __global__ __launch_bounds__(U3D_BLOCK) void preprocess_bwd_kernel(
     __syncthreads();
     if (threadIdx.x < 4) {
       const float v = s_qdot[0][threadIdx.x] + s_qdot[1][threadIdx.x] + s_qdot[2][threadIdx.x] + s_qdot[3][threadIdx.x];
-      unsafeAtomicAdd(&sink.qdot[item * 4 + threadIdx.x], v);
+      unsafeAtomicAdd(&sink.qdot[item * 4 + threadIdx.x], (double)v);
     }
   }
 }
@@ -772,7 +772,7 @@ __global__ __launch_bounds__(U3D_BLOCK) void preprocess_bwd_kernel(
 // across-point quaternion norms: qnorm[item][c] = || raw_rot[item, :, c] ||_2   (F.normalize(x(B,4,N), dim=-1))
 constexpr int QN_THREADS = 1024;   // one workgroup per set: 16 waves keep more of the strided loads in flight (7.5 -> ~4 us at P = 2048)
 __global__ __launch_bounds__(QN_THREADS) void quat_norms_kernel(U3DSpan span, const float* __restrict__ rots, int s_rots,
-                                                                float* __restrict__ qnorm, float* __restrict__ qdot_zero) {
+                                                                float* __restrict__ qnorm, double* __restrict__ qdot_zero) {
   __shared__ float sm[QN_THREADS / 64][4];
   const int item = blockIdx.x;
   int P;
@@ -796,13 +796,13 @@ __global__ __launch_bounds__(QN_THREADS) void quat_norms_kernel(U3DSpan span, co
 #pragma unroll
     for (int w = 0; w < QN_THREADS / 64; ++w) t += sm[w][threadIdx.x];
     qnorm[item * 4 + threadIdx.x] = sqrtf(t);
-    if (qdot_zero) qdot_zero[item * 4 + threadIdx.x] = 0.f;
+    if (qdot_zero) qdot_zero[item * 4 + threadIdx.x] = 0.0;
   }
 }
 
 // second term of the across-point normalise backward: d x_i -= x_i * (sum_j x_j g_j) / n^3  when n > eps
 __global__ __launch_bounds__(U3D_BLOCK) void quat_fixup_kernel(U3DSpan span, const float* __restrict__ rots, int s_rots,
-                                                               const float* __restrict__ qnorm, const float* __restrict__ qdot,
+                                                               const float* __restrict__ qnorm, const double* __restrict__ qdot,
                                                                float* __restrict__ d_rots) {
   const int item = blockIdx.y;
   int P;
@@ -814,7 +814,7 @@ __global__ __launch_bounds__(U3D_BLOCK) void quat_fixup_kernel(U3DSpan span, con
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float n = qnorm[item * 4 + k];
-    if (n > 1e-6f) d_rots[o + k] -= rots[o + k] * qdot[item * 4 + k] / (n * n * n);
+    if (n > 1e-6f) d_rots[o + k] -= rots[o + k] * (float)qdot[item * 4 + k] / (n * n * n);
   }
 }
 
@@ -888,11 +888,11 @@ void u3d_launch_preprocess_bwd(const u3d_raster_desc& d, const U3DBuffers& b, co
 #undef LAUNCH
 }
 
-void u3d_launch_quat_norms(const u3d_raster_desc& d, const float* rots, int s_rots, float* qnorm, float* qdot_zero, hipStream_t s) {
+void u3d_launch_quat_norms(const u3d_raster_desc& d, const float* rots, int s_rots, float* qnorm, double* qdot_zero, hipStream_t s) {
   hipLaunchKernelGGL(quat_norms_kernel, dim3(d.n_items), dim3(QN_THREADS), 0, s, u3d_span(d), rots, s_rots, qnorm, qdot_zero);
 }
 
-void u3d_launch_quat_fixup(const u3d_raster_desc& d, const float* rots, int s_rots, const float* qnorm, const float* qdot,
+void u3d_launch_quat_fixup(const u3d_raster_desc& d, const float* rots, int s_rots, const float* qnorm, const double* qdot,
                            float* d_rots, hipStream_t s) {
   hipLaunchKernelGGL(quat_fixup_kernel, dim3((d.P + U3D_BLOCK - 1) / U3D_BLOCK, d.n_items), dim3(U3D_BLOCK), 0, s, u3d_span(d), rots,
                      s_rots, qnorm, qdot, d_rots);

@@ -109,9 +109,11 @@ __device__ __forceinline__ float min_099(float a) {   // fminf(0.99f, a) without
 //     the walk keeps the NORMALISED remainder  rho_i = R_i / T_{i+1}  (the colour the pixel would show behind entry i, dotted
 //     with dL/dC; behind the last entry it is bg . dL/dC):
 //         d_i = c_i . dL/dC - rho_i,    dL/dalpha_i = T_i d_i,    rho_{i-1} = rho_i + alpha_i d_i,
-//     i.e. dL/dalpha_i = T_i (c_i . dL/dC) - R_i / (1 - alpha_i) with one subtraction, one FMA and one multiply.  The update is
-//     convex (rho stays between the colours it has seen), so nothing grows where T_final is ~1e-4; a pixel outside the image
-//     has Tr = 0, hence T_i = w = q = 0 whatever rho is;
+//     i.e. dL/dalpha_i = T_i (c_i . dL/dC) - R_i / (1 - alpha_i).  d_i is ONE chain of three FMAs seeded with -rho_i (a source
+//     modifier), the rho update one more.  The update is convex (rho stays between the colours it has seen), so nothing grows where
+//     T_final is ~1e-4; a pixel outside the image has Tr = 0, hence T_i = w = q = 0 whatever rho is.  The red channel meets -rho
+//     first: rho then cancels in the chain's first step, as it did against the finished sum.  (Forms measured and not kept -- T carried
+//     as its reciprocal, the limit-free entries as a loop of their own: EXPERIMENTS.md, round 7);
 //   * per pixel only q = dL/dG * G and the colour (depth) gradients are formed; a lane's pixels are dx0 - k, so its moments
 //     m0, mx, mxx come from q_0..q_3 and the run's centre, and  my = dy m0, mxy = dy mx, myy = dy my  per lane (a quad
 //     shares dy) before any cross-lane step;
@@ -390,7 +392,8 @@ __device__ __forceinline__ void tile_backward(const TileLds& L, const TileGeom& 
         const float araw = ar[k];   // opacity * G (alpha before the 0.99 clamp)
         const lanemask_t m_a = (PLAIN ? ~0ull : __builtin_amdgcn_fcmpf(pw, 0.f, U3D_FCMP_OLE)) & __builtin_amdgcn_fcmpf(araw, ALPHA_MIN, U3D_FCMP_OGE);
         // (Round 6 tried skipping the `pos < lim` compares for entries in front of the tile's EARLIEST limit -- a wave-uniform test per entry,
-        //  true for most of the walk: +3 % at C2 / C3, +1.7 % at C5.  The scalar branch costs more than the four compares and s_and it saves.)
+        //  true for most of the walk: +3 % at C2 / C3, +1.7 % at C5.  The scalar branch costs more than the four compares and s_and it saves.
+        //  Round 7 gave that zone a loop of its own, without a per-entry branch: no gain that can be told from the noise.  EXPERIMENTS.md.)
         ae[k] = mask_combine_sel0(m_a, __builtin_amdgcn_uicmp(pos, lim[k], U3D_ICMP_ULT), any, araw);
       }
       if (any == 0ull) continue;
@@ -403,9 +406,9 @@ __device__ __forceinline__ void tile_backward(const TileLds& L, const TileGeom& 
         const float Tn = Tr[k] * rc;            // T in front of this Gaussian
         const float w = alpha * Tn;
         Tr[k] = Tn;
-        float cdp = fmaf(R.x, dp2[k], fmaf(Q.w, dp1[k], Q.z * dp0[k]));
-        if (HAS_INVD) cdp = fmaf(invd, dinv[k], cdp);
-        const float dl = cdp - Rk[k];           // dL/dalpha = T_i dl
+        // c . dL/dC - rho as one chain seeded with -rho (the negation is a source modifier)
+        float dl = fmaf(R.x, dp2[k], fmaf(Q.w, dp1[k], fmaf(Q.z, dp0[k], -Rk[k])));   // dL/dalpha = T_i dl
+        if (HAS_INVD) dl = fmaf(invd, dinv[k], dl);
         Rk[k] = fmaf(alpha, dl, Rk[k]);         // convex step towards c . dL/dC: the remainder in front of this Gaussian
         q[k] = PLAIN ? w * dl : ae[k] * (Tn * dl);   // dL/dG * G  (PLAIN: ae == alpha, so ae T_i = w)
         if (k == 0) {
