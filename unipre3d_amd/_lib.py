@@ -1,5 +1,6 @@
 """ctypes binding of libunipre3d_rasterizer.so (the C-ABI declared in include/unipre3d_rasterizer.h), and the loader and call helpers
-every native library of the package is bound through (`open_library`, `check`, `ptr`, `stream_ptr`, `on_device`).
+every native library of the package is bound through (`open_library`, `call`, `on_device`, the argument coercions; `check`, `ptr` and
+`stream_ptr` are the pieces the rasterizer path and the tests use directly).
 
 The product path has NO CPU or PyTorch fallback: if the HIP library is missing or cannot be loaded,
 `load()` raises.  `import torch` must precede the dlopen so that the library's libamdhip64.so.7
@@ -118,7 +119,7 @@ def load() -> ctypes.CDLL:
 
 def check(code: int, what: str, named: bool = True) -> None:
     """Raises on a non-zero return code.  The rasterizer names its codes (u3d_error_string); the other libraries export no such
-    table and pass named=False."""
+    table (named=False) and are called through `call`."""
     if code != 0:
         if named:
             raise RuntimeError(f"{what} failed: {load().u3d_error_string(code).decode()} (code {code})")
@@ -160,10 +161,46 @@ def ptr(t) -> ctypes.c_void_p:
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+def call(fn, *args, dev, what=None, accept=()):
+    """One launching entry point of a library opened by open_library: fn(*args, stream).  A tensor goes in as its device pointer
+    (None stays NULL, everything else passes through), torch's current stream on `dev` comes last, as in every prototype under
+    include/.  Returns the code when it is 0 or listed in `accept`; any other code raises under the name `what` (default: the symbol)."""
+    code = fn(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], stream_ptr(dev))
+    if code != 0 and code not in accept:
+        raise RuntimeError(f"{what or fn.__name__} failed with code {code}")
+    return code
+
+
 def scratch(nbytes: int, dev):
     """(tensor that owns the bytes, 256-byte aligned device pointer into it)."""
     buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
     return buf, ctypes.c_void_p((buf.data_ptr() + 255) & ~255)
+
+
+def byte_buffer(nbytes: int, dev):
+    """A uint8 tensor of `nbytes` bytes, at least 16 (a zero-size query still gets a real pointer), as the allocator aligns it."""
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+
+def as_f32(t, what):
+    """The kernels read raw contiguous fp32: anything else (fp16/bf16 under autocast, float64, a strided view) is cast or copied,
+    never reinterpreted."""
+    if not t.is_floating_point():
+        raise TypeError(f"{what} must be a floating-point tensor, got {t.dtype}")
+    return (t if t.dtype == torch.float32 else t.float()).contiguous()
+
+
+def as_i32(t, what):
+    """Contiguous int32 indices from int32 or int64 (narrowed)."""
+    if t.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what} must be an int32 or int64 tensor, got {t.dtype}")
+    return (t if t.dtype == torch.int32 else t.int()).contiguous()
+
+
+def dense(t, shape):
+    """A contiguous, 16-byte aligned view (or copy) of a parameter in the library's shape, detached."""
+    t = t.detach().reshape(shape).contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
 
 
 def profile_begin(max_records: int = 65536, kinds=None, stride: int = 1) -> None:

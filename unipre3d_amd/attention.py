@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_attention.so")
 ABI_VERSION = 1
@@ -43,8 +43,7 @@ class _VarlenAttention(torch.autograd.Function):
         out = torch.empty(T, H, D, dtype=torch.float16, device=qkv.device)
         lse = torch.empty(H, T, dtype=torch.float32, device=qkv.device)
         if T > 0:
-            check(load().u3d_attn_varlen_fwd(_lib.ptr(qkv), _lib.ptr(cu_seqlens), _lib.ptr(out), _lib.ptr(lse), T, S, H, D, max_seqlen,
-                                             softmax_scale, stream_ptr(qkv.device)), "u3d_attn_varlen_fwd", named=False)
+            call(load().u3d_attn_varlen_fwd, qkv, cu_seqlens, out, lse, T, S, H, D, max_seqlen, softmax_scale, dev=qkv.device)
         ctx.save_for_backward(qkv, cu_seqlens, out, lse)
         ctx.args = (max_seqlen, softmax_scale)
         return out
@@ -57,9 +56,8 @@ class _VarlenAttention(torch.autograd.Function):
         dout = dout.to(torch.float16).contiguous()
         dqkv = torch.empty_like(qkv)
         if T > 0:
-            check(load().u3d_attn_varlen_bwd(_lib.ptr(qkv), _lib.ptr(cu_seqlens), _lib.ptr(out), _lib.ptr(dout), _lib.ptr(lse),
-                                             _lib.ptr(dqkv), T, cu_seqlens.numel() - 1, H, D, max_seqlen, softmax_scale,
-                                             stream_ptr(qkv.device)), "u3d_attn_varlen_bwd", named=False)
+            call(load().u3d_attn_varlen_bwd, qkv, cu_seqlens, out, dout, lse, dqkv, T, cu_seqlens.numel() - 1, H, D, max_seqlen,
+                 softmax_scale, dev=qkv.device)
         return dqkv, None, None, None
 
 

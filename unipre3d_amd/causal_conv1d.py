@@ -13,7 +13,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 ABI_VERSION = 1
 MIN_WIDTH, MAX_WIDTH = 2, 4
@@ -49,9 +49,7 @@ class _CausalConv1d(torch.autograd.Function):
         lib = load()
         Bsz, D, L = x.shape
         out = torch.empty(Bsz, D, L, dtype=torch.float32, device=x.device)
-        p = _lib.ptr
-        check(lib.u3d_cconv_fwd(p(x), p(weight), p(bias), p(out), x.stride(0), x.stride(1), Bsz, D, L, weight.shape[1], int(silu),
-                                stream_ptr(x.device)), "u3d_cconv_fwd", named=False)
+        call(lib.u3d_cconv_fwd, x, weight, bias, out, x.stride(0), x.stride(1), Bsz, D, L, weight.shape[1], int(silu), dev=x.device)
         ctx.save_for_backward(x, weight, bias)
         ctx.silu = silu
         return out
@@ -67,9 +65,8 @@ class _CausalConv1d(torch.autograd.Function):
         dbias = torch.empty_like(bias) if bias is not None else None
         nbytes = int(lib.u3d_cconv_bwd_scratch_bytes(Bsz, D))
         buf, base = _lib.scratch(nbytes, x.device)
-        p = _lib.ptr
-        check(lib.u3d_cconv_bwd(p(x), p(weight), p(bias), p(dout), p(dx), p(dweight), p(dbias), base, nbytes, x.stride(0), x.stride(1),
-                                Bsz, D, L, weight.shape[1], int(ctx.silu), stream_ptr(x.device)), "u3d_cconv_bwd", named=False)
+        call(lib.u3d_cconv_bwd, x, weight, bias, dout, dx, dweight, dbias, base, nbytes, x.stride(0), x.stride(1), Bsz, D, L,
+             weight.shape[1], int(ctx.silu), dev=x.device)
         return dx, dweight, dbias, None
 
 

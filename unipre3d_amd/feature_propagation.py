@@ -30,7 +30,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import as_f32, byte_buffer, call, on_device
 
 ABI_VERSION = 1
 MAX_POINTS, MAX_CHANNELS, TILE = 16384, 2048, 1024          # include/unipre3d_feature_propagation.h
@@ -49,12 +49,6 @@ EXPORTS = tuple(SIGNATURES)
 
 def load() -> ctypes.CDLL:
     return _lib.open_library("libunipre3d_feature_propagation.so", SIGNATURES, ("u3d_feature_propagation_abi_version", ABI_VERSION))
-
-
-def _f32(t, what):
-    if not t.is_floating_point():
-        raise TypeError(f"{what} must be a floating-point tensor, got {t.dtype}")
-    return (t if t.dtype == torch.float32 else t.float()).contiguous()
 
 
 def _check_clouds(xyz1, xyz2):
@@ -81,11 +75,10 @@ def neighbours(xyz1, xyz2):
     r_j = 1 / (d2_j + 1e-8).  With S == 1: idx = (0, 0, 0), weight = (1, 0, 0)."""
     B, N, S = _check_clouds(xyz1, xyz2)
     dev = on_device("feature_propagation", xyz1, xyz2)
-    xyz1, xyz2 = _f32(xyz1, "xyz1"), _f32(xyz2, "xyz2")
+    xyz1, xyz2 = as_f32(xyz1, "xyz1"), as_f32(xyz2, "xyz2")
     idx = torch.empty(B, N, 3, dtype=torch.int32, device=dev)
     weight = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
-    check(load().u3d_feature_propagation_search(_lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(idx), _lib.ptr(weight), B, N, S, stream_ptr(dev)),
-          "u3d_feature_propagation_search", named=False)
+    call(load().u3d_feature_propagation_search, xyz1, xyz2, idx, weight, B, N, S, dev=dev)
     return idx, weight
 
 
@@ -102,17 +95,14 @@ class _Propagate(torch.autograd.Function):
         D1 = 0 if points1 is None else points1.shape[1]
         dev = points2.device
         lib = load()
-        st = stream_ptr(dev)
         out = torch.empty(B, D1 + D2, N, dtype=torch.float32, device=dev)
-        check(lib.u3d_feature_propagation_fwd(_lib.ptr(idx), _lib.ptr(weight), _lib.ptr(points1), _lib.ptr(points2), _lib.ptr(out), B, N, S,
-                                              D1, D2, st), "u3d_feature_propagation_fwd", named=False)
+        call(lib.u3d_feature_propagation_fwd, idx, weight, points1, points2, out, B, N, S, D1, D2, dev=dev)
         ctx.dims = (B, N, S, D1, D2)
         if ctx.needs_input_grad[1]:
             ptr = torch.empty(B, S + 1, dtype=torch.int32, device=dev)
             ent = torch.empty(B, 3 * N, dtype=torch.int32, device=dev)
-            scratch = torch.empty(max(int(lib.u3d_feature_propagation_scratch_bytes(B, N, S)), 16), dtype=torch.uint8, device=dev)
-            check(lib.u3d_feature_propagation_lists(_lib.ptr(idx), _lib.ptr(ptr), _lib.ptr(ent), _lib.ptr(scratch), B, N, S, st),
-                  "u3d_feature_propagation_lists", named=False)
+            scratch = byte_buffer(lib.u3d_feature_propagation_scratch_bytes(B, N, S), dev)
+            call(lib.u3d_feature_propagation_lists, idx, ptr, ent, scratch, B, N, S, dev=dev)
             ctx.save_for_backward(ptr, ent, weight)
         return out
 
@@ -127,8 +117,7 @@ class _Propagate(torch.autograd.Function):
             if g.data_ptr() % 16 != 0:
                 g = g.clone()
             dpoints2 = torch.empty(B, D2, S, dtype=torch.float32, device=g.device)
-            check(load().u3d_feature_propagation_bwd(_lib.ptr(ptr), _lib.ptr(ent), _lib.ptr(weight), _lib.ptr(g), _lib.ptr(dpoints2), B, N, S,
-                                                     D1, D2, stream_ptr(g.device)), "u3d_feature_propagation_bwd", named=False)
+            call(load().u3d_feature_propagation_bwd, ptr, ent, weight, g, dpoints2, B, N, S, D1, D2, dev=g.device)
         return dpoints1, dpoints2, None, None
 
 
@@ -150,7 +139,7 @@ def propagate(xyz1, xyz2, points1, points2, neighbours=None):
     if D2 < 1 or D2 > MAX_CHANNELS or D1 > MAX_CHANNELS:
         raise NotImplementedError(f"D1={D1}, D2={D2} is not implemented (0 <= D1 <= {MAX_CHANNELS}, 1 <= D2 <= {MAX_CHANNELS})")
     override = neighbours
-    dev = on_device("feature_propagation", xyz1, xyz2, points1, points2, *(override or ()))
+    on_device("feature_propagation", xyz1, xyz2, points1, points2, *(override or ()))
     if override is None:
         idx, weight = _search(xyz1, xyz2)
     else:
@@ -161,11 +150,10 @@ def propagate(xyz1, xyz2, points1, points2, neighbours=None):
             raise NotImplementedError(f"neighbours: idx dtype {idx.dtype} is not implemented (int32 or int64)")
         if weight.requires_grad:
             raise NotImplementedError("neighbours: there is no gradient to the weights")
-        idx, weight = idx.to(torch.int32).contiguous(), _f32(weight, "weight")
-    stream_ptr(dev)
-    points2 = _f32(points2, "points2")
+        idx, weight = idx.to(torch.int32).contiguous(), as_f32(weight, "weight")
+    points2 = as_f32(points2, "points2")
     if points1 is not None:
-        points1 = _f32(points1, "points1")
+        points1 = as_f32(points1, "points1")
     return _Propagate.apply(points1, points2, idx, weight)
 
 

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_fusion.so")   # (U3D_LIB_DIRNAME: experiment builds, see _lib.py)
 ABI_VERSION = 2
@@ -40,9 +40,7 @@ class _ZBufferGather(torch.autograd.Function):
         sel = torch.empty(B, N, dtype=torch.int32, device=cp.device)
         # winner table: (depth bits << 32 | first winner) per pixel + the "empty pixel" bitmap behind it
         zbuf = torch.empty((load().u3d_zbuffer_fusion_zbuf_bytes(B, H, W) + 7) // 8, dtype=torch.int64, device=cp.device)
-        rc = load().u3d_zbuffer_fusion_forward(B, N, C, H, W, fx, fy, cx, cy, _lib.ptr(cp), _lib.ptr(feat), _lib.ptr(mapped),
-                                               _lib.ptr(sel), _lib.ptr(zbuf), stream_ptr(dev))
-        check(rc, "u3d_zbuffer_fusion_forward", named=False)
+        call(load().u3d_zbuffer_fusion_forward, B, N, C, H, W, fx, fy, cx, cy, cp, feat, mapped, sel, zbuf, dev=dev)
         ctx.save_for_backward(sel, zbuf)
         ctx.shape = (B, N, C, H, W)
         ctx.mark_non_differentiable(sel)
@@ -55,8 +53,7 @@ class _ZBufferGather(torch.autograd.Function):
         # gather form: the kernel writes every element of the (B,C,H,W) gradient exactly once (no zero-fill + scatter)
         grad_feat = torch.empty(B, C, H, W, dtype=torch.float32, device=sel.device)
         g = grad_mapped.contiguous().float()
-        rc = load().u3d_zbuffer_fusion_backward(B, N, C, H, W, _lib.ptr(g), _lib.ptr(sel), _lib.ptr(zbuf), _lib.ptr(grad_feat), stream_ptr(sel.device))
-        check(rc, "u3d_zbuffer_fusion_backward", named=False)
+        call(load().u3d_zbuffer_fusion_backward, B, N, C, H, W, g, sel, zbuf, grad_feat, dev=sel.device)
         return None, grad_feat, None, None, None, None
 
 

@@ -30,7 +30,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib, fusion
-from ._lib import check, on_device, stream_ptr
+from ._lib import byte_buffer, call, dense, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_image_fusion.so")
 ABI_VERSION = 1
@@ -52,16 +52,6 @@ EXPORTS = tuple(SIGNATURES)
 
 def load() -> ctypes.CDLL:
     return _lib.open_library("libunipre3d_image_fusion.so", SIGNATURES, ("u3d_imgfus_abi_version", ABI_VERSION))
-
-
-def _p(t):
-    return _lib.ptr(t)
-
-
-def _dense(t, shape):
-    """A contiguous, 16-byte aligned fp32 view (or copy) of a parameter in the library's shape."""
-    t = t.detach().reshape(shape).contiguous()
-    return t.clone() if t.data_ptr() % 16 else t
 
 
 def _check_map(x, num_groups):
@@ -88,9 +78,8 @@ def group_stats(x: torch.Tensor, num_groups: int, eps: float) -> torch.Tensor:
     lib = load()
     B, C, H, W = x.shape
     stats = torch.empty(B, num_groups, 2, dtype=torch.float32, device=dev)
-    scratch = torch.empty(max(16, lib.u3d_imgfus_stats_scratch_bytes(B, C, num_groups, H, W)), dtype=torch.uint8, device=dev)
-    check(lib.u3d_imgfus_stats(_p(x), B, C, num_groups, H, W, float(eps), _p(stats), _p(scratch), stream_ptr(dev)), "u3d_imgfus_stats",
-          named=False)
+    scratch = byte_buffer(lib.u3d_imgfus_stats_scratch_bytes(B, C, num_groups, H, W), dev)
+    call(lib.u3d_imgfus_stats, x, B, C, num_groups, H, W, float(eps), stats, scratch, dev=dev)
     return stats
 
 
@@ -101,7 +90,6 @@ class _SampleRows(torch.autograd.Function):
         B, Cin, H, W = x.shape
         N = cp.shape[1]
         Cout = weight.shape[0]
-        st = stream_ptr(dev)
         cp = cp.detach().contiguous().float()
         if cp.data_ptr() % 16:                       # (a slice of a larger tensor)
             cp = cp.clone()
@@ -109,12 +97,10 @@ class _SampleRows(torch.autograd.Function):
         sel = torch.empty(B, N, dtype=torch.int32, device=dev)
         flib = fusion.load()
         zbuf = torch.empty((flib.u3d_zbuffer_fusion_zbuf_bytes(B, H, W) + 7) // 8, dtype=torch.int64, device=dev)
-        check(flib.u3d_zbuffer_fusion_forward(B, N, Cin, H, W, fx, fy, cx, cy, _p(cp), _p(x), _p(rows), _p(sel), _p(zbuf), st),
-              "u3d_zbuffer_fusion_forward", named=False)
-        g, b, w, bi = _dense(gamma, (Cin,)), _dense(beta, (Cin,)), _dense(weight, (Cout, Cin)), _dense(bias, (Cout,))
+        call(flib.u3d_zbuffer_fusion_forward, B, N, Cin, H, W, fx, fy, cx, cy, cp, x, rows, sel, zbuf, dev=dev)
+        g, b, w, bi = dense(gamma, (Cin,)), dense(beta, (Cin,)), dense(weight, (Cout, Cin)), dense(bias, (Cout,))
         out = torch.empty(B, N, Cout, dtype=torch.float32, device=dev)
-        check(load().u3d_imgfus_rows_forward(_p(rows), _p(sel), _p(stats), _p(g), _p(b), _p(w), _p(bi), B, N, Cin, G, Cout, _p(out), st),
-              "u3d_imgfus_rows_forward", named=False)
+        call(load().u3d_imgfus_rows_forward, rows, sel, stats, g, b, w, bi, B, N, Cin, G, Cout, out, dev=dev)
         ctx.save_for_backward(rows, sel, stats, g, b, w)
         ctx.dims = (B, N, Cin, G, Cout)
         ctx.shapes = (gamma.shape, beta.shape, weight.shape, bias.shape)
@@ -134,9 +120,8 @@ class _SampleRows(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         dW, dbias = torch.empty(Cout, Cin, **f32), torch.empty(Cout, **f32)
         dgamma, dbeta = torch.empty(Cin, **f32), torch.empty(Cin, **f32)
-        scratch = torch.empty(max(16, lib.u3d_imgfus_backward_scratch_bytes(B, N, Cin, Cout)), dtype=torch.uint8, device=dev)
-        check(lib.u3d_imgfus_rows_backward(_p(dout), _p(rows), _p(sel), _p(stats), _p(g), _p(b), _p(w), B, N, Cin, G, Cout, _p(dW), _p(dbias),
-                                           _p(dgamma), _p(dbeta), _p(scratch), stream_ptr(dev)), "u3d_imgfus_rows_backward", named=False)
+        scratch = byte_buffer(lib.u3d_imgfus_backward_scratch_bytes(B, N, Cin, Cout), dev)
+        call(lib.u3d_imgfus_rows_backward, dout, rows, sel, stats, g, b, w, B, N, Cin, G, Cout, dW, dbias, dgamma, dbeta, scratch, dev=dev)
         sg, sb, sw, sbi = ctx.shapes
         return (dgamma.reshape(sg), dbeta.reshape(sb), dW.reshape(sw), dbias.reshape(sbi)) + (None,) * 8
 

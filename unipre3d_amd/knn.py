@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import as_f32, call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_knn.so")   # (U3D_LIB_DIRNAME: experiment builds, see _lib.py)
 MAX_K, TILE, QUERIES = 64, 2048, 16                           # include/unipre3d_knn.h: U3D_KNN_MAX_K, U3D_KNN_TILE, U3D_KNN_QUERIES
@@ -39,14 +39,6 @@ def load() -> ctypes.CDLL:
     return _lib.open_library("libunipre3d_knn.so", SIGNATURES)
 
 
-def _f32(t, what):
-    """The kernel reads raw contiguous fp32: anything else (fp16/bf16 under autocast, float64, a strided view) is cast or copied,
-    never reinterpreted."""
-    if not t.is_floating_point():
-        raise TypeError(f"{what} must be a floating-point tensor, got {t.dtype}")
-    return (t if t.dtype == torch.float32 else t.float()).contiguous()
-
-
 @torch.no_grad()
 def knn_query(k: int, support: torch.Tensor, query: torch.Tensor):
     """support (B,N,3), query (B,M,3) -> (dist2 (B,M,k) fp32 squared distances, idx (B,M,k) int32), ascending in (dist2, index)."""
@@ -59,10 +51,10 @@ def knn_query(k: int, support: torch.Tensor, query: torch.Tensor):
     M, k = query.size(1), int(k)
     if k < 1 or k > N or k > MAX_K:
         raise ValueError(f"k = {k} is outside 1..min(N = {N}, {MAX_K})")
-    support, query = _f32(support, "support"), _f32(query, "query")
+    support, query = as_f32(support, "support"), as_f32(query, "query")
     dist2 = torch.empty(B, M, k, dtype=torch.float32, device=dev)
     idx = torch.empty(B, M, k, dtype=torch.int32, device=dev)
-    check(load().u3d_knn(B, N, M, k, _lib.ptr(support), _lib.ptr(query), _lib.ptr(dist2), _lib.ptr(idx), stream_ptr(dev)), "knn", named=False)
+    call(load().u3d_knn, B, N, M, k, support, query, dist2, idx, dev=dev, what="knn")
     return dist2, idx
 
 

@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 from .causal_conv1d import load
 
 EXPORTS = ("u3d_addnorm_max_n", "u3d_addnorm_bwd_waves", "u3d_addnorm_bwd_scratch_bytes", "u3d_addnorm_fwd", "u3d_addnorm_bwd")
@@ -43,9 +43,7 @@ class _AddNorm(torch.autograd.Function):
         r = torch.empty_like(x2) if (residual is not None or prenorm) else None
         mean = torch.empty(M, dtype=torch.float32, device=dev) if not is_rms_norm else None
         rstd = torch.empty(M, dtype=torch.float32, device=dev)
-        p = _lib.ptr
-        check(lib.u3d_addnorm_fwd(p(x2), p(res2), p(weight), p(bias), p(y), p(r), p(mean), p(rstd), M, N, float(eps), int(is_rms_norm),
-                                  stream_ptr(dev)), "u3d_addnorm_fwd", named=False)
+        call(lib.u3d_addnorm_fwd, x2, res2, weight, bias, y, r, mean, rstd, M, N, float(eps), int(is_rms_norm), dev=dev)
         ctx.save_for_backward(r if r is not None else x2, weight, mean, rstd)
         ctx.cfg = (shape, residual is not None, bias is not None, prenorm, is_rms_norm)
         return (y.reshape(shape), r.reshape(shape)) if prenorm else y.reshape(shape)
@@ -64,9 +62,7 @@ class _AddNorm(torch.autograd.Function):
         dbias = torch.empty_like(weight) if has_bias else None
         nbytes = int(lib.u3d_addnorm_bwd_scratch_bytes(M, N))
         buf, base = _lib.scratch(nbytes, dev)
-        p = _lib.ptr
-        check(lib.u3d_addnorm_bwd(p(dy), p(dres), p(r), p(weight), p(mean), p(rstd), p(dx), p(dweight), p(dbias), base, nbytes, M, N,
-                                  int(is_rms_norm), stream_ptr(dev)), "u3d_addnorm_bwd", named=False)
+        call(lib.u3d_addnorm_bwd, dy, dres, r, weight, mean, rstd, dx, dweight, dbias, base, nbytes, M, N, int(is_rms_norm), dev=dev)
         dx = dx.reshape(shape)
         return dx, dweight, dbias, (dx if has_residual else None), None, None, None
 

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib, knn
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_lnp.so")
 ABI_VERSION = 1
@@ -79,8 +79,7 @@ def neighbours_from_idx(idx) -> Neighbours:
     B, G, K = idx.shape
     ptr = torch.empty(B, G + 1, dtype=torch.int32, device=dev)
     ent = torch.empty(B, G * K, dtype=torch.int32, device=dev)
-    check(load().u3d_lnp_neighbours(_lib.ptr(idx), _lib.ptr(ptr), _lib.ptr(ent), B, G, K, stream_ptr(dev)), "u3d_lnp_neighbours",
-          named=False)
+    call(load().u3d_lnp_neighbours, idx, ptr, ent, B, G, K, dev=dev)
     return Neighbours(idx, ptr, ent)
 
 
@@ -116,8 +115,7 @@ class _LocalNormPool(torch.autograd.Function):
         lse = torch.empty(B, G, C, dtype=torch.float32, device=dev)
         stats = torch.empty(4, dtype=torch.float32, device=dev)
         scratch = _scratch(lib.u3d_lnp_scratch_bytes(B, G, K, C, 0), dev)
-        check(lib.u3d_lnp_fwd(_lib.ptr(x), x.stride(0), _lib.ptr(nb.idx), _lib.ptr(alpha), _lib.ptr(beta), _lib.ptr(out), _lib.ptr(lse),
-                              _lib.ptr(stats), _lib.ptr(scratch), B, G, K, C, eps, stream_ptr(dev)), "u3d_lnp_fwd", named=False)
+        call(lib.u3d_lnp_fwd, x, x.stride(0), nb.idx, alpha, beta, out, lse, stats, scratch, B, G, K, C, eps, dev=dev)
         ctx.save_for_backward(x, alpha, beta, out, lse, stats)
         ctx.nb = nb
         return out
@@ -134,9 +132,8 @@ class _LocalNormPool(torch.autograd.Function):
         dx = torch.empty(B, G, C, dtype=torch.float32, device=dev)
         dalpha, dbeta = torch.empty(2 * C, dtype=torch.float32, device=dev), torch.empty(2 * C, dtype=torch.float32, device=dev)
         scratch = _scratch(lib.u3d_lnp_scratch_bytes(B, G, K, C, 1), dev)
-        check(lib.u3d_lnp_bwd(_lib.ptr(x), x.stride(0), _lib.ptr(nb.idx), _lib.ptr(nb.ptr), _lib.ptr(nb.ent), _lib.ptr(alpha),
-                              _lib.ptr(beta), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(stats), _lib.ptr(dout), _lib.ptr(dx),
-                              _lib.ptr(dalpha), _lib.ptr(dbeta), _lib.ptr(scratch), B, G, K, C, stream_ptr(dev)), "u3d_lnp_bwd", named=False)
+        call(lib.u3d_lnp_bwd, x, x.stride(0), nb.idx, nb.ptr, nb.ent, alpha, beta, out, lse, stats, dout, dx, dalpha, dbeta, scratch,
+             B, G, K, C, dev=dev)
         return dx, dalpha, dbeta, None, None
 
 

@@ -26,7 +26,7 @@ import torch
 from torch import nn
 
 from . import _lib, knn, pointops
-from ._lib import check, on_device, stream_ptr
+from ._lib import byte_buffer, call, on_device
 
 ABI_VERSION = 1
 MAX_POINTS, MAX_K, MAX_CHANNELS = 16384, 64, 512          # include/unipre3d_local_grouper.h
@@ -45,10 +45,6 @@ EXPORTS = tuple(SIGNATURES)
 
 def load() -> ctypes.CDLL:
     return _lib.open_library("libunipre3d_local_grouper.so", SIGNATURES, ("u3d_local_grouper_abi_version", ABI_VERSION))
-
-
-def _scratch(nbytes, dev):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
 
 
 def _strides(t, N, D):
@@ -76,7 +72,6 @@ class _LocalGroup(torch.autograd.Function):
         Cn, C = D + A, 2 * D + A
         dev = points.device
         lib = load()
-        st = stream_ptr(dev)
         sb, sp, sc = _strides(points, N, D)
         out = torch.empty((B, S, C, K) if cf else (B, S, K, C), dtype=torch.float32, device=dev)
         new_xyz = torch.empty(B, S, 3, dtype=torch.float32, device=dev)
@@ -84,19 +79,17 @@ class _LocalGroup(torch.autograd.Function):
         if normalize:
             mean = torch.empty(B, S, Cn, dtype=torch.float32, device=dev)
             stats = torch.empty(B, 4, dtype=torch.float32, device=dev)
-        scratch = _scratch(lib.u3d_local_grouper_scratch_bytes(B, N, S, K, D, int(use_xyz), normalize, 0), dev)
-        check(lib.u3d_local_grouper_fwd(_lib.ptr(xyz), _lib.ptr(points), sb, sp, sc, _lib.ptr(fps), _lib.ptr(idx), _lib.ptr(alpha),
-                                        _lib.ptr(beta), _lib.ptr(out), _lib.ptr(new_xyz), _lib.ptr(mean), _lib.ptr(stats), _lib.ptr(scratch),
-                                        B, N, S, K, D, int(use_xyz), normalize, int(cf), eps, st), "u3d_local_grouper_fwd", named=False)
+        scratch = byte_buffer(lib.u3d_local_grouper_scratch_bytes(B, N, S, K, D, int(use_xyz), normalize, 0), dev)
+        call(lib.u3d_local_grouper_fwd, xyz, points, sb, sp, sc, fps, idx, alpha, beta, out, new_xyz, mean, stats, scratch,
+             B, N, S, K, D, int(use_xyz), normalize, int(cf), eps, dev=dev)
         ctx.lists = None
         if any(ctx.needs_input_grad):
             ptr = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
             ent = torch.empty(B, S * K, dtype=torch.int32, device=dev)
             fptr = torch.empty(B, N + 1, dtype=torch.int32, device=dev)
             fent = torch.empty(B, S, dtype=torch.int32, device=dev)
-            ls = _scratch(lib.u3d_local_grouper_scratch_bytes(B, N, S, K, D, int(use_xyz), normalize, 2), dev)
-            check(lib.u3d_local_grouper_lists(_lib.ptr(fps), _lib.ptr(idx), _lib.ptr(ptr), _lib.ptr(ent), _lib.ptr(fptr), _lib.ptr(fent),
-                                              _lib.ptr(ls), B, N, S, K, st), "u3d_local_grouper_lists", named=False)
+            ls = byte_buffer(lib.u3d_local_grouper_scratch_bytes(B, N, S, K, D, int(use_xyz), normalize, 2), dev)
+            call(lib.u3d_local_grouper_lists, fps, idx, ptr, ent, fptr, fent, ls, B, N, S, K, dev=dev)
             ctx.lists = (ptr, ent, fptr, fent)
         ctx.save_for_backward(xyz, points, alpha, mean, stats)
         ctx.fps, ctx.idx = fps, idx
@@ -134,11 +127,9 @@ class _LocalGroup(torch.autograd.Function):
         dalpha = dbeta = None
         if normalize:
             dalpha, dbeta = torch.empty(Cn, dtype=torch.float32, device=dev), torch.empty(Cn, dtype=torch.float32, device=dev)
-        scratch = _scratch(lib.u3d_local_grouper_scratch_bytes(B, N, S, K, D, use_xyz, normalize, 1), dev)
-        check(lib.u3d_local_grouper_bwd(_lib.ptr(xyz), _lib.ptr(points), sb, sp, sc, _lib.ptr(fps), _lib.ptr(idx), _lib.ptr(ptr), _lib.ptr(ent),
-                                        _lib.ptr(fptr), _lib.ptr(fent), _lib.ptr(alpha), _lib.ptr(mean), _lib.ptr(stats), _lib.ptr(g),
-                                        _lib.ptr(dpoints), gb, gp, gc, _lib.ptr(dalpha), _lib.ptr(dbeta), _lib.ptr(scratch), B, N, S, K, D,
-                                        use_xyz, normalize, dcf, stream_ptr(dev)), "u3d_local_grouper_bwd", named=False)
+        scratch = byte_buffer(lib.u3d_local_grouper_scratch_bytes(B, N, S, K, D, use_xyz, normalize, 1), dev)
+        call(lib.u3d_local_grouper_bwd, xyz, points, sb, sp, sc, fps, idx, ptr, ent, fptr, fent, alpha, mean, stats, g,
+             dpoints, gb, gp, gc, dalpha, dbeta, scratch, B, N, S, K, D, use_xyz, normalize, dcf, dev=dev)
         return None, dpoints, dalpha, dbeta, None, None, None, None, None, None
 
 

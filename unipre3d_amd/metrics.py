@@ -23,8 +23,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
-from .knn import _f32
+from ._lib import as_f32, call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_metrics.so")
 TILE, HALO = 32, 5                                             # include/unipre3d_metrics.h: U3D_METRICS_TILE, U3D_METRICS_HALO
@@ -51,7 +50,7 @@ def _pair(img1, img2, what):
         raise ValueError(f"{what}: the two stacks differ in shape, {tuple(img1.shape)} and {tuple(img2.shape)}")
     if img1.dim() not in (3, 4):
         raise ValueError(f"{what}: (N,C,H,W) or (C,H,W) expected, got {tuple(img1.shape)}")
-    a, b = _f32(img1, "img1"), _f32(img2, "img2")
+    a, b = as_f32(img1, "img1"), as_f32(img2, "img2")
     if a.dim() == 3:
         a, b = a.unsqueeze(0), b.unsqueeze(0)
     if a.size(0) > 0 and min(a.shape[1:]) < 1:
@@ -70,8 +69,7 @@ def _forward(dev, a, b, save):
     all_zero = torch.empty(N, dtype=torch.int32, device=dev)
     dmaps = torch.empty((3, N, C, H, W), dtype=torch.float32, device=dev) if save else None
     if N:
-        check(lib.u3d_metrics_forward(N, C, H, W, _lib.ptr(a), _lib.ptr(b), _lib.ptr(partial), _lib.ptr(ssim_n), _lib.ptr(sqsum),
-                                      _lib.ptr(all_zero), _lib.ptr(dmaps), stream_ptr(dev)), "metrics forward", named=False)
+        call(lib.u3d_metrics_forward, N, C, H, W, a, b, partial, ssim_n, sqsum, all_zero, dmaps, dev=dev, what="metrics forward")
     return ssim_n, sqsum, all_zero, dmaps
 
 
@@ -90,11 +88,10 @@ class _SSIM(torch.autograd.Function):
     def backward(ctx, grad):
         a, b, dmaps = ctx.saved_tensors
         N, C, H, W = a.shape
-        weight = _f32(grad, "grad_output")
+        weight = as_f32(grad, "grad_output")
         out = torch.empty_like(a)
         if N:
-            check(load().u3d_metrics_ssim_backward(N, C, H, W, _lib.ptr(a), _lib.ptr(b), _lib.ptr(dmaps), _lib.ptr(weight), _lib.ptr(out),
-                                                   stream_ptr(a.device)), "ssim backward", named=False)
+            call(load().u3d_metrics_ssim_backward, N, C, H, W, a, b, dmaps, weight, out, dev=a.device, what="ssim backward")
         return out, None, None
 
 

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_mha.so")
 ABI_VERSION = 1
@@ -41,8 +41,7 @@ class _PackedAttention(torch.autograd.Function):
         B, N, _, H, D = qkv.shape
         out = torch.empty(B, N, H, D, dtype=torch.float32, device=qkv.device)
         lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device)
-        check(load().u3d_mha_fwd(_lib.ptr(qkv), _lib.ptr(out), _lib.ptr(lse), B, N, H, D, softmax_scale, stream_ptr(qkv.device)),
-              "u3d_mha_fwd", named=False)
+        call(load().u3d_mha_fwd, qkv, out, lse, B, N, H, D, softmax_scale, dev=qkv.device)
         ctx.save_for_backward(qkv, out, lse)
         ctx.softmax_scale = softmax_scale
         return out
@@ -53,8 +52,7 @@ class _PackedAttention(torch.autograd.Function):
         B, N, _, H, D = qkv.shape
         dout = dout.to(torch.float32).contiguous()
         dqkv = torch.empty_like(qkv)
-        check(load().u3d_mha_bwd(_lib.ptr(qkv), _lib.ptr(out), _lib.ptr(dout), _lib.ptr(lse), _lib.ptr(dqkv), B, N, H, D,
-                                 ctx.softmax_scale, stream_ptr(qkv.device)), "u3d_mha_bwd", named=False)
+        call(load().u3d_mha_bwd, qkv, out, dout, lse, dqkv, B, N, H, D, ctx.softmax_scale, dev=qkv.device)
         return dqkv, None
 
 

@@ -37,7 +37,7 @@ from torch.autograd import Function
 
 from . import _lib
 from . import pointops as _pointops
-from ._lib import check, on_device, stream_ptr
+from ._lib import as_f32, as_i32, call, on_device
 
 __all__ = ["knn_query_raw", "knnquery", "knn_query", "ballquery", "furthestsampling", "grouping", "subtraction", "aggregation",
            "interpolation2", "interpolation", "querygroup", "queryandgroup"]
@@ -60,28 +60,10 @@ SIGNATURES = {   # include/unipre3d_offsetops.h
     "u3d_offset_aggregate_backward": (_i, [_i, _i, _i, _i] + [_vp] * 9),
 }
 EXPORTS = tuple(SIGNATURES)
-_p = _lib.ptr
 
 
 def load() -> ctypes.CDLL:
     return _lib.open_library("libunipre3d_offsetops.so", SIGNATURES)
-
-
-def _f32(t, what):
-    """The kernels read raw contiguous fp32: anything else is cast or copied, never reinterpreted."""
-    if not t.is_floating_point():
-        raise TypeError(f"{what} must be a floating-point tensor, got {t.dtype}")
-    return (t if t.dtype == torch.float32 else t.float()).contiguous()
-
-
-def _i32(t, what):
-    if t.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"{what} must be an int32 or int64 tensor, got {t.dtype}")
-    return (t if t.dtype == torch.int32 else t.int()).contiguous()
-
-
-def _call(name, *args):
-    check(getattr(load(), name)(*args), name, named=False)
 
 
 def _search_args(nsample, xyz, new_xyz, offset, new_offset):
@@ -99,7 +81,7 @@ def _search_args(nsample, xyz, new_xyz, offset, new_offset):
     if nsample < 1 or nsample > MAX_K:
         raise ValueError(f"nsample = {nsample} is outside 1..{MAX_K}")
     dev = on_device("offset_ops", xyz, new_xyz, offset, new_offset)
-    return nsample, _f32(xyz, "xyz"), _f32(new_xyz, "new_xyz"), _i32(offset, "offset"), _i32(new_offset, "new_offset"), dev
+    return nsample, as_f32(xyz, "xyz"), as_f32(new_xyz, "new_xyz"), as_i32(offset, "offset"), as_i32(new_offset, "new_offset"), dev
 
 
 @torch.no_grad()
@@ -111,7 +93,7 @@ def knn_query_raw(nsample, xyz, new_xyz, offset, new_offset):
         return (torch.full((m, k), FILL_DIST2, dtype=torch.float32, device=dev), torch.full((m, k), -1, dtype=torch.int32, device=dev))
     dist2 = torch.empty(m, k, dtype=torch.float32, device=dev)
     idx = torch.empty(m, k, dtype=torch.int32, device=dev)
-    _call("u3d_offset_knn", b, n, m, k, _p(xyz), _p(new_xyz), _p(offset), _p(new_offset), _p(dist2), _p(idx), stream_ptr(dev))
+    call(load().u3d_offset_knn, b, n, m, k, xyz, new_xyz, offset, new_offset, dist2, idx, dev=dev)
     return dist2, idx
 
 
@@ -135,7 +117,7 @@ def ballquery(radius, nsample, xyz, new_xyz, offset, new_offset):
     if b == 0:
         return torch.zeros(m, ns, dtype=torch.int32, device=dev)
     idx = torch.empty(m, ns, dtype=torch.int32, device=dev)
-    _call("u3d_offset_ballquery", b, n, m, float(radius), ns, _p(xyz), _p(new_xyz), _p(offset), _p(new_offset), _p(idx), stream_ptr(dev))
+    call(load().u3d_offset_ballquery, b, n, m, float(radius), ns, xyz, new_xyz, offset, new_offset, idx, dev=dev)
     return idx
 
 
@@ -154,7 +136,7 @@ def furthestsampling(xyz, offset, new_offset, m=None):
     if offset.dim() != 1 or new_offset.dim() != 1 or offset.numel() != new_offset.numel():
         raise ValueError(f"offset (b) and new_offset (b) expected, got {tuple(offset.shape)} and {tuple(new_offset.shape)}")
     dev = on_device("offset_ops", xyz, offset, new_offset)
-    xyz, offset, new_offset = _f32(xyz, "xyz"), _i32(offset, "offset"), _i32(new_offset, "new_offset")
+    xyz, offset, new_offset = as_f32(xyz, "xyz"), as_i32(offset, "offset"), as_i32(new_offset, "new_offset")
     n, b = xyz.size(0), offset.numel()
     if m is None:
         m = int(new_offset[-1]) if b else 0
@@ -164,18 +146,17 @@ def furthestsampling(xyz, offset, new_offset, m=None):
     idx = torch.full((m,), -1, dtype=torch.int32, device=dev)
     if b == 0 or m == 0:
         return idx
-    rc = _pointops.load().u3d_offset_furthest_sampling(b, n, m, _p(xyz), _p(offset), _p(new_offset), _p(_pointops.grid_workspace(b, dev)),
-                                                       _p(idx), stream_ptr(dev))
+    rc = call(_pointops.load().u3d_offset_furthest_sampling, b, n, m, xyz, offset, new_offset, _pointops.grid_workspace(b, dev), idx,
+              dev=dev, accept=(_pointops.STATUS_OVER_CAPACITY,))
     if rc == _pointops.STATUS_OVER_CAPACITY:
         raise RuntimeError(f"furthestsampling: {n} rows in {b} segments are beyond the grid kernel's capacity")
-    check(rc, "u3d_offset_furthest_sampling", named=False)
     return idx
 
 
 def _idx2(idx, rows, what):
     if idx.dim() != 2 or idx.size(0) != rows:
         raise ValueError(f"{what}: idx ({rows},nsample) expected, got {tuple(idx.shape)}")
-    return _i32(idx, "idx")
+    return as_i32(idx, "idx")
 
 
 def _out(empty, *shape, dev):
@@ -192,10 +173,10 @@ class Grouping(Function):
             raise ValueError(f"grouping: input (n,c) expected, got {tuple(input.shape)}")
         dev = on_device("offset_ops", input, idx)
         idx = _idx2(idx, idx.size(0) if idx.dim() == 2 else -1, "grouping")
-        x = _f32(input, "input")
+        x = as_f32(input, "input")
         (n, c), (m, ns) = x.shape, idx.shape
         out = torch.empty(m, ns, c, dtype=torch.float32, device=dev)
-        _call("u3d_offset_group_forward", m, ns, c, n, _p(x), _p(idx), _p(out), stream_ptr(dev))
+        call(load().u3d_offset_group_forward, m, ns, c, n, x, idx, out, dev=dev)
         ctx.n, ctx.in_dtype = n, input.dtype
         ctx.save_for_backward(idx)
         return out
@@ -203,10 +184,10 @@ class Grouping(Function):
     @staticmethod
     def backward(ctx, grad_output):
         idx, = ctx.saved_tensors
-        g = _f32(grad_output, "grad_output")
+        g = as_f32(grad_output, "grad_output")
         m, ns, c = g.shape
         grad = _out(m * ns == 0, ctx.n, c, dev=g.device)
-        _call("u3d_offset_group_backward", m, ns, c, ctx.n, _p(g), _p(idx), _p(grad), stream_ptr(g.device))
+        call(load().u3d_offset_group_backward, m, ns, c, ctx.n, g, idx, grad, dev=g.device)
         return grad.to(ctx.in_dtype), None
 
 
@@ -222,10 +203,10 @@ class Subtraction(Function):
             raise ValueError(f"subtraction: two (n,c) inputs expected, got {tuple(input1.shape)} and {tuple(input2.shape)}")
         dev = on_device("offset_ops", input1, input2, idx)
         idx = _idx2(idx, input1.size(0), "subtraction")
-        a, b2 = _f32(input1, "input1"), _f32(input2, "input2")
+        a, b2 = as_f32(input1, "input1"), as_f32(input2, "input2")
         (n, c), ns = a.shape, idx.size(1)
         out = torch.empty(n, ns, c, dtype=torch.float32, device=dev)
-        _call("u3d_offset_subtract_forward", n, ns, c, _p(a), _p(b2), _p(idx), _p(out), stream_ptr(dev))
+        call(load().u3d_offset_subtract_forward, n, ns, c, a, b2, idx, out, dev=dev)
         ctx.dtypes = (input1.dtype, input2.dtype)
         ctx.save_for_backward(idx)
         return out
@@ -233,11 +214,11 @@ class Subtraction(Function):
     @staticmethod
     def backward(ctx, grad_output):
         idx, = ctx.saved_tensors
-        g = _f32(grad_output, "grad_output")
+        g = as_f32(grad_output, "grad_output")
         n, ns, c = g.shape
         g1 = torch.empty(n, c, dtype=torch.float32, device=g.device)
         g2 = torch.empty(n, c, dtype=torch.float32, device=g.device)
-        _call("u3d_offset_subtract_backward", n, ns, c, _p(idx), _p(g), _p(g1), _p(g2), stream_ptr(g.device))
+        call(load().u3d_offset_subtract_backward, n, ns, c, idx, g, g1, g2, dev=g.device)
         return g1.to(ctx.dtypes[0]), g2.to(ctx.dtypes[1]), None
 
 
@@ -262,9 +243,9 @@ class Aggregation(Function):
         idx = _idx2(idx, n, "aggregation")
         if idx.size(1) != ns:
             raise ValueError(f"aggregation: idx ({n},{ns}) expected, got {tuple(idx.shape)}")
-        x, p, w = _f32(input, "input"), _f32(position, "position"), _f32(weight, "weight")
+        x, p, w = as_f32(input, "input"), as_f32(position, "position"), as_f32(weight, "weight")
         out = torch.empty(n, c, dtype=torch.float32, device=dev)
-        _call("u3d_offset_aggregate_forward", n, ns, c, w_c, _p(x), _p(p), _p(w), _p(idx), _p(out), stream_ptr(dev))
+        call(load().u3d_offset_aggregate_forward, n, ns, c, w_c, x, p, w, idx, out, dev=dev)
         ctx.dtypes = (input.dtype, position.dtype, weight.dtype)
         ctx.save_for_backward(x, p, w, idx)
         return out
@@ -272,13 +253,13 @@ class Aggregation(Function):
     @staticmethod
     def backward(ctx, grad_output):
         x, p, w, idx = ctx.saved_tensors
-        g = _f32(grad_output, "grad_output")
+        g = as_f32(grad_output, "grad_output")
         n, ns, c = p.shape
         w_c, dev = w.size(2), g.device
         gx = torch.empty(n, c, dtype=torch.float32, device=dev)
         gp = torch.empty(n, ns, c, dtype=torch.float32, device=dev)
         gw = torch.empty(n, ns, w_c, dtype=torch.float32, device=dev)
-        _call("u3d_offset_aggregate_backward", n, ns, c, w_c, _p(x), _p(p), _p(w), _p(idx), _p(g), _p(gx), _p(gp), _p(gw), stream_ptr(dev))
+        call(load().u3d_offset_aggregate_backward, n, ns, c, w_c, x, p, w, idx, g, gx, gp, gw, dev=dev)
         return gx.to(ctx.dtypes[0]), gp.to(ctx.dtypes[1]), gw.to(ctx.dtypes[2]), None
 
 
@@ -298,10 +279,10 @@ class _WeightedGather(Function):
     @staticmethod
     def forward(ctx, input, idx, weight):
         dev = on_device("offset_ops", input, idx, weight)
-        x, w, idx = _f32(input, "input"), _f32(weight, "weight"), _i32(idx, "idx")
+        x, w, idx = as_f32(input, "input"), as_f32(weight, "weight"), as_i32(idx, "idx")
         (m_in, c), (n_out, k) = x.shape, idx.shape
         out = torch.empty(n_out, c, dtype=torch.float32, device=dev)
-        _call("u3d_offset_interpolate_forward", n_out, c, k, m_in, _p(x), _p(idx), _p(w), _p(out), stream_ptr(dev))
+        call(load().u3d_offset_interpolate_forward, n_out, c, k, m_in, x, idx, w, out, dev=dev)
         ctx.m_in, ctx.in_dtype = m_in, input.dtype
         ctx.save_for_backward(idx, w)
         return out
@@ -309,10 +290,10 @@ class _WeightedGather(Function):
     @staticmethod
     def backward(ctx, grad_output):
         idx, w = ctx.saved_tensors
-        g = _f32(grad_output, "grad_output")
+        g = as_f32(grad_output, "grad_output")
         n_out, c = g.shape
         grad = _out(n_out * idx.size(1) == 0, ctx.m_in, c, dev=g.device)
-        _call("u3d_offset_interpolate_backward", n_out, c, idx.size(1), ctx.m_in, _p(g), _p(idx), _p(w), _p(grad), stream_ptr(g.device))
+        call(load().u3d_offset_interpolate_backward, n_out, c, idx.size(1), ctx.m_in, g, idx, w, grad, dev=g.device)
         return grad.to(ctx.in_dtype), None, None
 
 

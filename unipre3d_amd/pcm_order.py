@@ -29,9 +29,8 @@ import ctypes
 
 import torch
 
-from . import _lib
 from . import serialization as _ser
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 ORDERS = {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3, "xyz": 4, "xzy": 5, "yxz": 6, "yzx": 7, "zxy": 8, "zyx": 9}
 META_HEAD, GATHER_MAX, MAX_CHANNELS = 8, 8, 2048          # include/unipre3d_serialization.h
@@ -77,7 +76,6 @@ def _gather(index, tensors):
     """[t[index] for t in tensors], each (rows, C_t) fp32 contiguous: one launch per GATHER_MAX tensors."""
     lib = _ser.load()
     rows, dev = index.shape[0], index.device
-    st = stream_ptr(dev)
     outs = [torch.empty_like(t) for t in tensors]
     for k in range(0, len(tensors), GATHER_MAX):
         src, dst = tensors[k:k + GATHER_MAX], outs[k:k + GATHER_MAX]
@@ -85,8 +83,8 @@ def _gather(index, tensors):
         srcs = (ctypes.c_void_p * T)(*[t.data_ptr() for t in src])
         dsts = (ctypes.c_void_p * T)(*[t.data_ptr() for t in dst])
         chans = (ctypes.c_int32 * T)(*[t.shape[1] for t in src])
-        check(lib.u3d_ser_gather_rows(rows, T, _lib.ptr(index), ctypes.cast(srcs, ctypes.c_void_p), ctypes.cast(dsts, ctypes.c_void_p),
-                                      ctypes.cast(chans, ctypes.c_void_p), st), "u3d_ser_gather_rows", named=False)
+        call(lib.u3d_ser_gather_rows, rows, T, index, ctypes.cast(srcs, ctypes.c_void_p), ctypes.cast(dsts, ctypes.c_void_p),
+             ctypes.cast(chans, ctypes.c_void_p), dev=dev)
     return outs
 
 
@@ -150,8 +148,7 @@ def point_order(pos, order, grid_size=0.02, check=False):
     code = torch.empty(rows, dtype=torch.int64, device=dev)
     index, inverse = torch.empty_like(code), torch.empty_like(code)
     scratch = torch.empty(lib.u3d_ser_scratch_bytes(1, rows), dtype=torch.uint8, device=dev)
-    _lib.check(lib.u3d_ser_pcm_order(B, N, _lib.ptr(pos), gs, oid, _lib.ptr(grid), _lib.ptr(meta), _lib.ptr(code), _lib.ptr(index),
-                                     _lib.ptr(inverse), _lib.ptr(scratch), stream_ptr(dev)), "u3d_ser_pcm_order", named=False)
+    call(lib.u3d_ser_pcm_order, B, N, pos, gs, oid, grid, meta, code, index, inverse, scratch, dev=dev)
     if check and int(meta[4].item()):
         raise ValueError(f"pos / grid_size={grid_size}: a cell needs more than 16 bits (depth {int(meta[3].item())}) or is not finite")
     return index, inverse, code

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_pointfusion.so")
 ABI_VERSION = 2
@@ -63,9 +63,8 @@ def _min_rows(min_coord, S, dev):
 def _voxelize(coord, grid_size, mins, min_stride, origin, S, offsets, n_max, n, scratch, meta):
     dev = coord.device
     voxel_offsets = torch.empty(S + 1, dtype=torch.int32, device=dev)
-    check(load().u3d_pointfusion_voxelize(n_max, n, S, _lib.ptr(offsets), _lib.ptr(coord), _lib.ptr(mins), min_stride,
-                                          origin, float(np.float32(grid_size)), _lib.ptr(meta), _lib.ptr(voxel_offsets), _lib.ptr(scratch),
-                                          stream_ptr(dev)), "u3d_pointfusion_voxelize", named=False)
+    call(load().u3d_pointfusion_voxelize, n_max, n, S, offsets, coord, mins, min_stride, origin, float(np.float32(grid_size)), meta,
+         voxel_offsets, scratch, dev=dev)
     return voxel_offsets
 
 
@@ -82,10 +81,8 @@ def _pick(M, n_max, S, offsets, voxel_offsets, coord, mins, min_stride, origin, 
     out_coord = torch.empty(M, 3, dtype=torch.float32, device=dev)
     grid = torch.empty(M, 3, dtype=torch.int64, device=dev)
     src = torch.empty(M, dtype=torch.int32, device=dev) if src_map is not None else None
-    check(load().u3d_pointfusion_pick(M, n_max, S, _lib.ptr(offsets), _lib.ptr(voxel_offsets), _lib.ptr(coord), _lib.ptr(mins),
-                                      min_stride, origin, float(np.float32(grid_size)), MODES[mode], int(part), _lib.ptr(draws), seed,
-                                      _lib.ptr(src_map), _lib.ptr(index), _lib.ptr(out_coord), _lib.ptr(grid), _lib.ptr(src),
-                                      _lib.ptr(scratch), stream_ptr(dev)), "u3d_pointfusion_pick", named=False)
+    call(load().u3d_pointfusion_pick, M, n_max, S, offsets, voxel_offsets, coord, mins, min_stride, origin, float(np.float32(grid_size)),
+         MODES[mode], int(part), draws, seed, src_map, index, out_coord, grid, src, scratch, dev=dev)
     return index, out_coord, grid, src
 
 
@@ -121,8 +118,7 @@ def grid_sample(coord, grid_size=0.02, min_coord=None, mode="train", draws=None,
     lib = load()
     if min_coord is None:
         mins = torch.empty(S, 6, dtype=torch.float32, device=dev)
-        check(lib.u3d_pointfusion_minmax(N, S, _lib.ptr(offsets), _lib.ptr(coord), _lib.ptr(mins), stream_ptr(dev)),
-              "u3d_pointfusion_minmax", named=False)
+        call(lib.u3d_pointfusion_minmax, N, S, offsets, coord, mins, dev=dev)
         stride, origin = 6, 1
     else:
         mins, stride, origin = _min_rows(min_coord, S, dev), 3, 0
@@ -136,8 +132,7 @@ def grid_sample(coord, grid_size=0.02, min_coord=None, mode="train", draws=None,
            "max_count": max_count}
     if return_inverse:
         inverse = torch.empty(N, dtype=torch.int64, device=dev)
-        check(lib.u3d_pointfusion_inverse(N, N, S, _lib.ptr(offsets), _lib.ptr(voxel_offsets), _lib.ptr(inverse), _lib.ptr(scratch),
-                                          stream_ptr(dev)), "u3d_pointfusion_inverse", named=False)
+        call(lib.u3d_pointfusion_inverse, N, N, S, offsets, voxel_offsets, inverse, scratch, dev=dev)
         out["inverse"] = inverse
     return out
 
@@ -153,8 +148,7 @@ class _PixelGather(torch.autograd.Function):
             raise ValueError(f"feat_2d_all: expected float32, got {f.dtype}")
         M = src.shape[0]
         out = torch.empty(M, C, dtype=torch.float32, device=f.device)
-        check(load().u3d_pointfusion_gather_forward(M, C, H * W, _lib.ptr(f), _lib.ptr(src), _lib.ptr(out), stream_ptr(f.device)),
-              "u3d_pointfusion_gather_forward", named=False)
+        call(load().u3d_pointfusion_gather_forward, M, C, H * W, f, src, out, dev=f.device)
         ctx.save_for_backward(src)
         ctx.shape = (V, C, H, W)
         return out
@@ -166,8 +160,7 @@ class _PixelGather(torch.autograd.Function):
         g = grad_out.contiguous().float()
         grad = torch.empty(V, C, H, W, dtype=torch.float32, device=src.device)   # every element written once by the kernel
         pixel_map = torch.empty(V * H * W, dtype=torch.int32, device=src.device)
-        check(load().u3d_pointfusion_gather_backward(V, C, H * W, src.shape[0], _lib.ptr(g), _lib.ptr(src), _lib.ptr(pixel_map),
-                                                     _lib.ptr(grad), stream_ptr(src.device)), "u3d_pointfusion_gather_backward", named=False)
+        call(load().u3d_pointfusion_gather_backward, V, C, H * W, src.shape[0], g, src, pixel_map, grad, dev=src.device)
         return grad, None
 
 
@@ -196,13 +189,12 @@ def fuse_pixels(feat_2d_all, unprojected_coord, init_coord, grid_size=0.02, mode
     init = init_coord.detach().float().contiguous()
     lib = load()
     box = torch.empty(1, 6, dtype=torch.float32, device=dev)    # min xyz, max xyz of init_coord: the box and the grid origin
-    check(lib.u3d_pointfusion_minmax(init.shape[0], 1, None, _lib.ptr(init), _lib.ptr(box), stream_ptr(dev)), "u3d_pointfusion_minmax", named=False)
+    call(lib.u3d_pointfusion_minmax, init.shape[0], 1, None, init, box, dev=dev)
     scratch = torch.empty(lib.u3d_pointfusion_scratch_bytes(P, 1), dtype=torch.uint8, device=dev)
     meta = torch.empty(4, dtype=torch.int32, device=dev)
     coord = torch.empty(P, 3, dtype=torch.float32, device=dev)
     src_of_point = torch.empty(P, dtype=torch.int32, device=dev)
-    check(lib.u3d_pointfusion_compact(P, _lib.ptr(uc), _lib.ptr(box), _lib.ptr(coord), _lib.ptr(src_of_point), _lib.ptr(meta),
-                                      _lib.ptr(scratch), stream_ptr(dev)), "u3d_pointfusion_compact", named=False)
+    call(lib.u3d_pointfusion_compact, P, uc, box, coord, src_of_point, meta, scratch, dev=dev)
     voxel_offsets = _voxelize(coord, grid_size, box, 6, 0, 1, None, P, -1, scratch, meta)
     n, M, _, _ = meta.tolist()                      # the call's one device -> host read
     if n == 0:

@@ -13,7 +13,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_pointops.so")   # (U3D_LIB_DIRNAME: experiment builds, see _lib.py)
 CONTRACTIONS = {"fma_llvm": 0, "fma_chain": 1, "none": 2}    # include/unipre3d_pointops.h: U3D_PO_*
@@ -55,9 +55,6 @@ EXPORTS = tuple(SIGNATURES)
 
 def load() -> ctypes.CDLL:
     return _lib.open_library("libunipre3d_pointops.so", SIGNATURES)
-
-
-_stream = stream_ptr   # (kept name: callers of the raw C-ABI entry points outside this module take the stream through it)
 
 
 def _f32(t, what):
@@ -114,13 +111,12 @@ class FurthestPointSampling(Function):
         B, N, _ = xyz.size()
         out = torch.empty(B, npoint, dtype=torch.int32, device=xyz.device)
         if N > N_GRID and B > 0 and npoint > 0:
-            rc = load().u3d_furthest_point_sampling_grid(B, N, npoint, _lib.ptr(xyz), _lib.ptr(grid_workspace(B, xyz.device)), _lib.ptr(out),
-                                                         stream_ptr(dev))
+            rc = call(load().u3d_furthest_point_sampling_grid, B, N, npoint, xyz, grid_workspace(B, xyz.device), out, dev=dev,
+                      what="fps (grid)", accept=(STATUS_OVER_CAPACITY,))
             if rc != STATUS_OVER_CAPACITY:
-                check(rc, "fps (grid)", named=False)
                 return out
         temp = torch.empty(B, N, dtype=torch.float32, device=xyz.device) if N > 8192 else None
-        check(load().u3d_furthest_point_sampling(B, N, npoint, _lib.ptr(xyz), _lib.ptr(temp), _lib.ptr(out), stream_ptr(dev)), "fps", named=False)
+        call(load().u3d_furthest_point_sampling, B, N, npoint, xyz, temp, out, dev=dev, what="fps")
         return out
 
     @staticmethod
@@ -141,7 +137,7 @@ class GatherOperation(Function):
         B, npoint = idx.size()
         _, C, N = features.size()
         out = torch.empty(B, C, npoint, dtype=torch.float32, device=features.device)
-        check(load().u3d_gather_points(B, C, N, npoint, _lib.ptr(features), _lib.ptr(idx), _lib.ptr(out), stream_ptr(dev)), "gather", named=False)
+        call(load().u3d_gather_points, B, C, N, npoint, features, idx, out, dev=dev, what="gather")
         ctx.for_backwards = (idx, C, N)
         return out
 
@@ -151,8 +147,7 @@ class GatherOperation(Function):
         B, npoint = idx.size()
         grad = torch.zeros(B, C, N, dtype=torch.float32, device=grad_out.device)
         g = _f32(grad_out, "grad_out").contiguous()
-        check(load().u3d_gather_points_grad(B, C, N, npoint, _lib.ptr(g), _lib.ptr(idx), _lib.ptr(grad), stream_ptr(on_device("pointops", g, idx))),
-              "gather grad", named=False)
+        call(load().u3d_gather_points_grad, B, C, N, npoint, g, idx, grad, dev=on_device("pointops", g, idx), what="gather grad")
         return grad, None
 
 
@@ -175,8 +170,7 @@ class GroupingOperation(Function):
         B, npoint, nsample = idx.size()
         _, C, N = features.size()
         out = torch.empty(B, C, npoint, nsample, dtype=torch.float32, device=features.device)
-        check(load().u3d_group_points(B, C, N, npoint, nsample, _lib.ptr(features), _lib.ptr(idx), _lib.ptr(out), stream_ptr(dev)),
-              "group", named=False)
+        call(load().u3d_group_points, B, C, N, npoint, nsample, features, idx, out, dev=dev, what="group")
         ctx.for_backwards = (idx, N)
         return out
 
@@ -186,8 +180,7 @@ class GroupingOperation(Function):
         B, C, npoint, nsample = grad_out.size()
         grad = torch.zeros(B, C, N, dtype=torch.float32, device=grad_out.device)
         g = _f32(grad_out, "grad_out").contiguous()
-        check(load().u3d_group_points_grad(B, C, N, npoint, nsample, _lib.ptr(g), _lib.ptr(idx), _lib.ptr(grad),
-                                           stream_ptr(on_device("pointops", g, idx))), "group grad", named=False)
+        call(load().u3d_group_points_grad, B, C, N, npoint, nsample, g, idx, grad, dev=on_device("pointops", g, idx), what="group grad")
         return grad, None
 
 
@@ -204,8 +197,7 @@ class BallQuery(Function):
         B, N, _ = xyz.size()
         npoint = new_xyz.size(1)
         idx = torch.empty(B, npoint, nsample, dtype=torch.int32, device=xyz.device)
-        check(load().u3d_ball_query(B, N, npoint, float(radius), nsample, _lib.ptr(new_xyz), _lib.ptr(xyz), _lib.ptr(idx), stream_ptr(dev)),
-              "ball query", named=False)
+        call(load().u3d_ball_query, B, N, npoint, float(radius), nsample, new_xyz, xyz, idx, dev=dev, what="ball query")
         return idx
 
     @staticmethod
@@ -228,8 +220,7 @@ class ThreeNN(Function):
         m = known.size(1)
         dist2 = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
         idx = torch.empty(B, N, 3, dtype=torch.int32, device=dev)
-        check(load().u3d_three_nn(B, N, m, _lib.ptr(unknown), _lib.ptr(known), _lib.ptr(dist2), _lib.ptr(idx), stream_ptr(dev)),
-              "three_nn", named=False)
+        call(load().u3d_three_nn, B, N, m, unknown, known, dist2, idx, dev=dev, what="three_nn")
         return torch.sqrt(dist2), idx
 
     @staticmethod
@@ -252,8 +243,7 @@ class ThreeInterpolate(Function):
         n = idx.size(1)
         ctx.three_interpolate_for_backward = (idx, weight, m)
         out = torch.empty(B, c, n, dtype=torch.float32, device=dev)
-        check(load().u3d_three_interpolate(B, c, m, n, _lib.ptr(features), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(out), stream_ptr(dev)),
-              "three_interpolate", named=False)
+        call(load().u3d_three_interpolate, B, c, m, n, features, idx, weight, out, dev=dev, what="three_interpolate")
         return out
 
     @staticmethod
@@ -262,8 +252,8 @@ class ThreeInterpolate(Function):
         B, c, n = grad_out.size()
         grad_features = torch.zeros(B, c, m, dtype=torch.float32, device=grad_out.device)
         g = _f32(grad_out, "grad_out").contiguous()
-        check(load().u3d_three_interpolate_grad(B, c, n, m, _lib.ptr(g), _lib.ptr(idx), _lib.ptr(weight), _lib.ptr(grad_features),
-                                                stream_ptr(on_device("pointops", g, idx, weight))), "three_interpolate grad", named=False)
+        call(load().u3d_three_interpolate_grad, B, c, n, m, g, idx, weight, grad_features, dev=on_device("pointops", g, idx, weight),
+             what="three_interpolate grad")
         return grad_features, None, None
 
 

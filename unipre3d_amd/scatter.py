@@ -10,8 +10,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 from .attention import load
 
 REDUCE = {"sum": 0, "add": 0, "mean": 1, "max": 2, "min": 3}
@@ -25,8 +24,7 @@ class _SegmentCSR(torch.autograd.Function):
         M = indptr.numel() - 1
         out = torch.empty(M, C, dtype=torch.float32, device=src.device)
         arg = torch.empty(M, C, dtype=torch.int64, device=src.device) if reduce >= 2 else None
-        check(load().u3d_segment_csr_fwd(_lib.ptr(src), _lib.ptr(indptr), _lib.ptr(out), _lib.ptr(arg), N, M, C, reduce,
-                                         stream_ptr(src.device)), "u3d_segment_csr_fwd", named=False)
+        call(load().u3d_segment_csr_fwd, src, indptr, out, arg, N, M, C, reduce, dev=src.device)
         ctx.save_for_backward(indptr, arg)
         ctx.args = (N, M, C, reduce)
         ctx.mark_non_differentiable(indptr)
@@ -38,8 +36,7 @@ class _SegmentCSR(torch.autograd.Function):
         N, M, C, reduce = ctx.args
         dout = dout.to(torch.float32).contiguous()
         dsrc = torch.empty(N, C, dtype=torch.float32, device=dout.device)
-        check(load().u3d_segment_csr_bwd(_lib.ptr(dout), _lib.ptr(indptr), _lib.ptr(arg), _lib.ptr(dsrc), N, M, C, reduce,
-                                         stream_ptr(dout.device)), "u3d_segment_csr_bwd", named=False)
+        call(load().u3d_segment_csr_bwd, dout, indptr, arg, dsrc, N, M, C, reduce, dev=dout.device)
         return dsrc, None, None
 
 

@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_selective_scan.so")
 ABI_VERSION = 1
@@ -50,9 +50,8 @@ class _SelectiveScan(torch.autograd.Function):
         out = torch.empty_like(u)
         last = torch.empty(Bsz, Dm, D_STATE, dtype=torch.float32, device=u.device) if return_last_state else None
         xsave = torch.empty(Bsz, Dm, npass, D_STATE, dtype=torch.float32, device=u.device) if npass > 1 else None
-        p = _lib.ptr
-        check(lib.u3d_sscan_fwd(p(u), p(delta), p(A), p(B), p(C), p(D), p(z), p(delta_bias), p(out), p(last), p(xsave),
-                                Bsz, Dm, G, D_STATE, L, int(delta_softplus), stream_ptr(u.device)), "u3d_sscan_fwd", named=False)
+        call(lib.u3d_sscan_fwd, u, delta, A, B, C, D, z, delta_bias, out, last, xsave, Bsz, Dm, G, D_STATE, L, int(delta_softplus),
+             dev=u.device)
         ctx.save_for_backward(u, delta, A, B, C, D, z, delta_bias, xsave)
         ctx.delta_softplus = bool(delta_softplus)
         if return_last_state:
@@ -75,10 +74,8 @@ class _SelectiveScan(torch.autograd.Function):
         dbias = torch.empty_like(delta_bias) if delta_bias is not None else None
         nbytes = int(lib.u3d_sscan_bwd_scratch_bytes(Bsz, Dm, G, L))
         buf, base = _lib.scratch(nbytes, dev)
-        p = _lib.ptr
-        check(lib.u3d_sscan_bwd(p(u), p(delta), p(A), p(B), p(C), p(D), p(z), p(delta_bias), p(dout), p(xsave), p(du), p(ddelta), p(dA),
-                                p(dB), p(dC), p(dD), p(dz), p(dbias), base, nbytes, Bsz, Dm, G, D_STATE, L,
-                                int(ctx.delta_softplus), stream_ptr(dev)), "u3d_sscan_bwd", named=False)
+        call(lib.u3d_sscan_bwd, u, delta, A, B, C, D, z, delta_bias, dout, xsave, du, ddelta, dA, dB, dC, dD, dz, dbias, base, nbytes,
+             Bsz, Dm, G, D_STATE, L, int(ctx.delta_softplus), dev=dev)
         return du, ddelta, dA, dB, dC, dD, dz, dbias, None, None
 
 

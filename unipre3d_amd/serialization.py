@@ -21,7 +21,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_serialization.so")
 ABI_VERSION = 1
@@ -134,9 +134,8 @@ def encode(grid_coord, batch=None, depth=16, order="z"):
     dev, _ = _check_points(grid_coord, batch, depth, None)
     N = grid_coord.shape[0]
     code = torch.empty(K, N, dtype=torch.int64, device=dev)
-    check(lib.u3d_ser_encode(N, _lib.ptr(grid_coord), int(grid_coord.dtype == torch.int64), _lib.ptr(batch),
-                             int(batch is not None and batch.dtype == torch.int64), depth, K, bits, _lib.ptr(code), stream_ptr(dev)),
-          "u3d_ser_encode", named=False)
+    call(lib.u3d_ser_encode, N, grid_coord, int(grid_coord.dtype == torch.int64), batch,
+         int(batch is not None and batch.dtype == torch.int64), depth, K, bits, code, dev=dev)
     return code[0] if isinstance(order, str) else code
 
 
@@ -149,8 +148,7 @@ def sort_codes(code, key_bits=63):
         raise ValueError(f"key_bits={key_bits}: 1 .. 63")
     order, inverse = torch.empty_like(code), torch.empty_like(code)
     scratch = _scratch(lib, K, N, dev)
-    check(lib.u3d_ser_sort(K, N, int(key_bits), _lib.ptr(code), _lib.ptr(order), _lib.ptr(inverse), _lib.ptr(scratch), stream_ptr(dev)),
-          "u3d_ser_sort", named=False)
+    call(lib.u3d_ser_sort, K, N, int(key_bits), code, order, inverse, scratch, dev=dev)
     return order, inverse
 
 
@@ -166,9 +164,8 @@ def serialize(grid_coord, batch, depth, orders, batch_size=None, shuffle_orders=
     code = torch.empty(K, N, dtype=torch.int64, device=dev)
     order, inverse = torch.empty_like(code), torch.empty_like(code)
     scratch = _scratch(lib, K, N, dev)
-    check(lib.u3d_ser_serialize(N, _lib.ptr(grid_coord), int(grid_coord.dtype == torch.int64), _lib.ptr(batch),
-                                int(batch is not None and batch.dtype == torch.int64), depth, K, bits, key_bits, _lib.ptr(code),
-                                _lib.ptr(order), _lib.ptr(inverse), _lib.ptr(scratch), stream_ptr(dev)), "u3d_ser_serialize", named=False)
+    call(lib.u3d_ser_serialize, N, grid_coord, int(grid_coord.dtype == torch.int64), batch,
+         int(batch is not None and batch.dtype == torch.int64), depth, K, bits, key_bits, code, order, inverse, scratch, dev=dev)
     if shuffle_orders:
         perm = torch.randperm(K).to(dev)
         code, order, inverse = code[perm], order[perm], inverse[perm]
@@ -211,8 +208,7 @@ def patch_padding(offset, patch_size, device=None):
     pad = torch.empty(T_pad, dtype=torch.int64, device=dev)
     unpad = torch.empty(T, dtype=torch.int64, device=dev)
     cu = torch.empty(S + 1, dtype=torch.int32, device=dev)
-    check(lib.u3d_ser_patch_padding(B, P, T, T_pad, S, _lib.ptr(meta), _lib.ptr(pad), _lib.ptr(unpad), _lib.ptr(cu), stream_ptr(dev)),
-          "u3d_ser_patch_padding", named=False)
+    call(lib.u3d_ser_patch_padding, B, P, T, T_pad, S, meta, pad, unpad, cu, dev=dev)
     return pad, unpad, cu
 
 
@@ -232,15 +228,13 @@ def pool_clusters(code, pooling_depth, depth=None, batch_size=None):
         if not 1 <= int(depth) <= 16 or pd > int(depth) or int(batch_size) < 1 or 3 * int(depth) + int(batch_size).bit_length() > 63:
             raise ValueError(f"depth={depth}, batch_size={batch_size}, pooling_depth={pd}: not a serialization's")
         key_bits = max(3 * (int(depth) - pd) + (int(batch_size) - 1).bit_length(), 1)
-    st = stream_ptr(dev)
     scratch = _scratch(lib, K, N, dev)
     meta = torch.empty(4, dtype=torch.int32, device=dev)
-    check(lib.u3d_ser_pool_count(K, N, 3 * pd, key_bits, _lib.ptr(code), _lib.ptr(meta), _lib.ptr(scratch), st), "u3d_ser_pool_count", named=False)
+    call(lib.u3d_ser_pool_count, K, N, 3 * pd, key_bits, code, meta, scratch, dev=dev)
     M = int(meta[0].item())                    # the one device -> host read: the cluster count
     new = lambda *shape: torch.empty(*shape, dtype=torch.int64, device=dev)
     cluster, indices, idx_ptr, head = new(N), new(N), new(M + 1), new(M)
     pcode, porder, pinverse = new(K, M), new(K, M), new(K, M)
-    check(lib.u3d_ser_pool_emit(K, N, M, 3 * pd, key_bits, _lib.ptr(code), _lib.ptr(cluster), _lib.ptr(indices), _lib.ptr(idx_ptr),
-                                _lib.ptr(head), _lib.ptr(pcode), _lib.ptr(porder), _lib.ptr(pinverse), _lib.ptr(scratch), st),
-          "u3d_ser_pool_emit", named=False)
+    call(lib.u3d_ser_pool_emit, K, N, M, 3 * pd, key_bits, code, cluster, indices, idx_ptr, head, pcode, porder, pinverse, scratch,
+         dev=dev)
     return cluster, indices, idx_ptr, head, pcode, porder, pinverse

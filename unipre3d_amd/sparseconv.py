@@ -32,7 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import call, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_sparseconv.so")
 ABI_VERSION = 1
@@ -104,8 +104,7 @@ def subm_map(indices, spatial_shape, batch_size, k) -> SubMMap:
     first = torch.empty(N, dtype=torch.int32, device=dev)
     nxt = torch.empty(N, dtype=torch.int32, device=dev)
     scratch = torch.empty(max(lib.u3d_spconv_scratch_bytes(N), 1), dtype=torch.uint8, device=dev)
-    check(lib.u3d_spconv_subm_map(N, _lib.ptr(idx), int(batch_size), D[0], D[1], D[2], k, _lib.ptr(table), _lib.ptr(first),
-                                  _lib.ptr(nxt), _lib.ptr(scratch), stream_ptr(dev)), "u3d_spconv_subm_map", named=False)
+    call(lib.u3d_spconv_subm_map, N, idx, int(batch_size), D[0], D[1], D[2], k, table, first, nxt, scratch, dev=dev)
     return SubMMap(k, table, first, nxt)
 
 
@@ -119,9 +118,7 @@ def down_map(indices, spatial_shape, batch_size, s) -> DownMap:
     lib = load()
     scratch = torch.empty(max(lib.u3d_spconv_scratch_bytes(N), 1), dtype=torch.uint8, device=dev)
     meta = torch.empty(4, dtype=torch.int32, device=dev)
-    st = stream_ptr(dev)
-    check(lib.u3d_spconv_down_map(N, _lib.ptr(idx), int(batch_size), D[0], D[1], D[2], s, _lib.ptr(meta), _lib.ptr(scratch), st),
-          "u3d_spconv_down_map", named=False)
+    call(lib.u3d_spconv_down_map, N, idx, int(batch_size), D[0], D[1], D[2], s, meta, scratch, dev=dev)
     M = int(meta[0].item())                    # the map's one device -> host read: the output count
     out_indices = torch.empty(M, 4, dtype=torch.int32, device=dev)
     table = torch.empty(M, K, dtype=torch.int32, device=dev)
@@ -129,9 +126,8 @@ def down_map(indices, spatial_shape, batch_size, s) -> DownMap:
     nxt = torch.empty(N, dtype=torch.int32, device=dev)
     list_row = torch.empty(N, dtype=torch.int32, device=dev)
     list_src = torch.empty(N, dtype=torch.int32, device=dev)
-    check(lib.u3d_spconv_down_emit(N, M, _lib.ptr(idx), int(batch_size), D[0], D[1], D[2], s, _lib.ptr(out_indices), _lib.ptr(table),
-                                   _lib.ptr(first), _lib.ptr(nxt), _lib.ptr(list_row), _lib.ptr(list_src), _lib.ptr(scratch), st),
-          "u3d_spconv_down_emit", named=False)
+    call(lib.u3d_spconv_down_emit, N, M, idx, int(batch_size), D[0], D[1], D[2], s, out_indices, table, first, nxt, list_row, list_src,
+         scratch, dev=dev)
     out_shape = [(d - s) // s + 1 for d in D]
     return DownMap(s, idx, D, out_indices, out_shape, table, first, nxt, list_row, list_src)
 
@@ -143,15 +139,13 @@ def _gemm(R, K, A, W, bias, table, list_row=None, mask=None, out_rows=None):
     if A.shape[0] == 0:   # a strided conv that dropped every row: no entry has a source, the rows are bias (or 0); never read
         A = A.new_zeros(1, Cin)
     Y = torch.empty(R if out_rows is None else out_rows, Cout, dtype=torch.float32, device=A.device)
-    check(load().u3d_spconv_gemm(R, K, Cin, Cout, _lib.ptr(table), _lib.ptr(list_row), _lib.ptr(A), _lib.ptr(W), _lib.ptr(bias),
-                                 _lib.ptr(mask), _lib.ptr(Y), stream_ptr(A.device)), "u3d_spconv_gemm", named=False)
+    call(load().u3d_spconv_gemm, R, K, Cin, Cout, table, list_row, A, W, bias, mask, Y, dev=A.device)
     return Y
 
 
 def _dupsum(X, first, nxt):
     out = torch.empty_like(X)
-    check(load().u3d_spconv_dupsum(X.shape[0], X.shape[1], _lib.ptr(first), _lib.ptr(nxt), _lib.ptr(X), _lib.ptr(out),
-                                   stream_ptr(X.device)), "u3d_spconv_dupsum", named=False)
+    call(load().u3d_spconv_dupsum, X.shape[0], X.shape[1], first, nxt, X, out, dev=X.device)
     return out
 
 
@@ -161,8 +155,7 @@ def _wgrad(R, K, A, G, table, gather_g):
     lib = load()
     part = torch.empty(max(lib.u3d_spconv_wgrad_partial_floats(R, K, Cin, Cout), 1), dtype=torch.float32, device=A.device)
     dW = torch.empty(K, Cin, Cout, dtype=torch.float32, device=A.device)
-    check(lib.u3d_spconv_wgrad(R, K, Cin, Cout, _lib.ptr(table), int(gather_g), _lib.ptr(A), _lib.ptr(G), _lib.ptr(part), _lib.ptr(dW),
-                               stream_ptr(A.device)), "u3d_spconv_wgrad", named=False)
+    call(lib.u3d_spconv_wgrad, R, K, Cin, Cout, table, int(gather_g), A, G, part, dW, dev=A.device)
     return dW
 
 
@@ -171,7 +164,7 @@ def _colsum(G):
     lib = load()
     part = torch.empty(max(lib.u3d_spconv_colsum_partial_floats(R, C), 1), dtype=torch.float32, device=G.device)
     db = torch.empty(C, dtype=torch.float32, device=G.device)
-    check(lib.u3d_spconv_colsum(R, C, _lib.ptr(G), _lib.ptr(part), _lib.ptr(db), stream_ptr(G.device)), "u3d_spconv_colsum", named=False)
+    call(lib.u3d_spconv_colsum, R, C, G, part, db, dev=G.device)
     return db
 
 

@@ -26,7 +26,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import check, on_device, stream_ptr
+from ._lib import byte_buffer, call, dense, on_device
 
 LIB_PATH = os.path.join(_lib.LIB_DIR, "libunipre3d_tokenizer.so")
 ABI_VERSION = 1
@@ -55,23 +55,13 @@ def load() -> ctypes.CDLL:
     return _lib.open_library("libunipre3d_tokenizer.so", SIGNATURES, ("u3d_tok_abi_version", ABI_VERSION))
 
 
-def _p(t):
-    return _lib.ptr(t)
-
-
 def _xargs(x):
     B, G, n, _ = x.shape
-    return [_p(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), B, G, n]
-
-
-def _dense(t, shape):
-    """A contiguous, 16-byte aligned fp32 view (or copy) of a parameter in the library's shape."""
-    t = t.detach().reshape(shape).contiguous()
-    return t.clone() if t.data_ptr() % 16 else t
+    return [x, x.stride(0), x.stride(1), x.stride(2), x.stride(3), B, G, n]
 
 
 def _scratch(lib, M, n, C, phase, training, dev):
-    return torch.empty(max(16, lib.u3d_tok_scratch_bytes(M, n, C, phase, int(training))), dtype=torch.uint8, device=dev)
+    return byte_buffer(lib.u3d_tok_scratch_bytes(M, n, C, phase, int(training)), dev)
 
 
 def _reduced(block, stat_reduce, keep_local):
@@ -99,8 +89,7 @@ class _Tokenize(torch.autograd.Function):
         rows = M * n
         C = params[10].shape[0]
         W1, b1, g1, be1, W2, b2, W3, b3, g2, be2, W4, b4 = (
-            _dense(p, s) for p, s in zip(params, ((C1, 3), (C1,), (C1,), (C1,), (C2, C1), (C2,), (C3, C3), (C3,), (C3,), (C3,), (C, C3), (C,))))
-        st = stream_ptr(dev)
+            dense(p, s) for p, s in zip(params, ((C1, 3), (C1,), (C1,), (C1,), (C2, C1), (C2,), (C3, C3), (C3,), (C3,), (C3,), (C, C3), (C,))))
         f32 = dict(dtype=torch.float32, device=dev)
         training = cfg.training
         reduce = cfg.stat_reduce if training else None
@@ -111,22 +100,19 @@ class _Tokenize(torch.autograd.Function):
         sums1 = sums2 = loc1 = loc2 = None
         if training:
             sums1 = torch.empty(10, dtype=torch.float64, device=dev)
-            check(lib.u3d_tok_moments(*_xargs(x), _p(sums1), _p(_scratch(lib, M, n, 1, 0, 1, dev)), st), "u3d_tok_moments", named=False)
+            call(lib.u3d_tok_moments, *_xargs(x), sums1, _scratch(lib, M, n, 1, 0, 1, dev), dev=dev)
             loc1, sums1 = sums1, _reduced(sums1, reduce, True)
             sums2 = torch.empty(1 + 2 * C3, dtype=torch.float64, device=dev)
         fold1, fold2 = torch.empty(FOLD1_FLOATS, **f32), torch.empty(FOLD2_FLOATS, **f32)
         f2, y3 = torch.empty(rows, C2, **f32), torch.empty(rows, C3, **f32)
         g, arg2 = torch.empty(M, C2, **f32), torch.empty(M, C2, dtype=torch.int32, device=dev)
-        check(lib.u3d_tok_fwd_a(*_xargs(x), _p(W1), _p(b1), _p(g1), _p(be1), _p(W2), _p(b2), _p(W3), _p(b3), _p(sums1),
-                                _p(rm1), _p(rv1), _p(nbt1), cfg.eps[0], mom[0], _p(fold1),
-                                _p(f2), _p(g), _p(arg2), _p(y3), _p(sums2), _p(_scratch(lib, M, n, 1, 1, training, dev)), st),
-              "u3d_tok_fwd_a", named=False)
+        call(lib.u3d_tok_fwd_a, *_xargs(x), W1, b1, g1, be1, W2, b2, W3, b3, sums1, rm1, rv1, nbt1, cfg.eps[0], mom[0], fold1,
+             f2, g, arg2, y3, sums2, _scratch(lib, M, n, 1, 1, training, dev), dev=dev)
         if training:
             loc2, sums2 = sums2, _reduced(sums2, reduce, True)
         out, arg4 = torch.empty(B, G, C, **f32), torch.empty(M, C, dtype=torch.int32, device=dev)
-        check(lib.u3d_tok_fwd_b(_p(y3), M, n, C, _p(g2), _p(be2), _p(W4), _p(b4), _p(sums2), _p(rm2), _p(rv2),
-                                _p(nbt2), cfg.eps[1], mom[1], _p(fold2), _p(out), _p(arg4),
-                                _p(_scratch(lib, M, n, C, 2, 1, dev)), st), "u3d_tok_fwd_b", named=False)
+        call(lib.u3d_tok_fwd_b, y3, M, n, C, g2, be2, W4, b4, sums2, rm2, rv2, nbt2, cfg.eps[1], mom[1], fold2, out, arg4,
+             _scratch(lib, M, n, C, 2, 1, dev), dev=dev)
         ctx.save_for_backward(x, W1, g1, W2, W3, g2, W4, fold1, fold2, f2, y3, g, arg2, arg4)
         ctx.cfg, ctx.shapes = cfg, [p.shape for p in params]
         ctx.fwd_sums = (loc1, sums1, loc2, sums2)         # this process's and the reduced statistics blocks (None in eval mode)
@@ -143,7 +129,6 @@ class _Tokenize(torch.autograd.Function):
         M = B * G
         rows = M * n
         C = W4.shape[0]
-        st = stream_ptr(dev)
         f32 = dict(dtype=torch.float32, device=dev)
         training = int(cfg.training)
         reduce = cfg.stat_reduce if cfg.training else None
@@ -152,22 +137,20 @@ class _Tokenize(torch.autograd.Function):
             dout = dout.clone()
         dW4, db4, dh3m = torch.empty(C, C3, **f32), torch.empty(C, **f32), torch.empty(rows, C3, **f32)
         sums3 = torch.empty(1 + 2 * C3, dtype=torch.float64, device=dev)
-        check(lib.u3d_tok_bwd_1(_p(dout), _p(y3), _p(arg4), _p(fold2), _p(W4), M, n, C, _p(dW4), _p(db4), _p(dh3m), _p(sums3),
-                                _p(_scratch(lib, M, n, C, 3, 1, dev)), st), "u3d_tok_bwd_1", named=False)
+        call(lib.u3d_tok_bwd_1, dout, y3, arg4, fold2, W4, M, n, C, dW4, db4, dh3m, sums3, _scratch(lib, M, n, C, 3, 1, dev), dev=dev)
         red3 = _reduced(sums3, reduce, True)
         dg2, dbe2, dW3, db3 = torch.empty(C3, **f32), torch.empty(C3, **f32), torch.empty(C3, C3, **f32), torch.empty(C3, **f32)
         dW2, db2 = torch.empty(C2, C1, **f32), torch.empty(C2, **f32)
         df2, dh1m = torch.empty(rows, C2, **f32), torch.empty(rows, C1, **f32)
         sums1b = torch.empty(1 + 2 * C1, dtype=torch.float64, device=dev)
-        check(lib.u3d_tok_bwd_2(*_xargs(x), _p(dh3m), _p(y3), _p(f2), _p(g), _p(arg2), _p(fold1), _p(fold2), _p(g2), _p(loc2), _p(sums2),
-                                _p(sums3), _p(red3), training, _p(W2), _p(W3), _p(dg2), _p(dbe2), _p(dW3), _p(db3), _p(dW2), _p(db2), _p(df2), _p(dh1m),
-                                _p(sums1b), _p(_scratch(lib, M, n, 1, 4, 1, dev)), st), "u3d_tok_bwd_2", named=False)
+        call(lib.u3d_tok_bwd_2, *_xargs(x), dh3m, y3, f2, g, arg2, fold1, fold2, g2, loc2, sums2, sums3, red3, training, W2, W3,
+             dg2, dbe2, dW3, db3, dW2, db2, df2, dh1m, sums1b, _scratch(lib, M, n, 1, 4, 1, dev), dev=dev)
         del dh3m, df2
         red1 = _reduced(sums1b, reduce, True)
         dg1, dbe1, dW1, db1 = torch.empty(C1, **f32), torch.empty(C1, **f32), torch.empty(C1, 3, **f32), torch.empty(C1, **f32)
         dx = torch.empty(B, G, n, 3, **f32) if (ctx.needs_input_grad[0] or cfg.need_dx) else None
-        check(lib.u3d_tok_bwd_3(*_xargs(x), _p(dh1m), _p(fold1), _p(g1), _p(loc1), _p(sums1), _p(sums1b), _p(red1), training, _p(W1), _p(dg1), _p(dbe1),
-                                _p(dW1), _p(db1), _p(dx), _p(_scratch(lib, M, n, 1, 5, 1, dev)), st), "u3d_tok_bwd_3", named=False)
+        call(lib.u3d_tok_bwd_3, *_xargs(x), dh1m, fold1, g1, loc1, sums1, sums1b, red1, training, W1, dg1, dbe1, dW1, db1, dx,
+             _scratch(lib, M, n, 1, 5, 1, dev), dev=dev)
         grads = (dW1, db1, dg1, dbe1, dW2, db2, dW3, db3, dg2, dbe2, dW4, db4)
         return (dx if ctx.needs_input_grad[0] else None, None) + tuple(t.view(s) for t, s in zip(grads, ctx.shapes))
 
